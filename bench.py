@@ -17,9 +17,13 @@ Multi-GPU: one process per GPU (torchrun); problems shard as contiguous slices
 of the one generated set; no collective in the data path (weak scaling).  The
 barrier + synchronize bracket the timed region; the time is the MAX over ranks.
 
-Prints ONE JSON line on rank 0 with `roofline` (the whole-solve launch, HIP
-events on its stream) and `cpu_baseline` (the reference's CPU PyTorch op
-structure restated in fp32 torch, oracle/torch_cpu.py, on the host cores).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the
+steps, writes the last step's outputs (--dump-outputs DIR) and prints the
+headline figure.  --full adds what takes runs of its own: `roofline` (the
+whole-solve launch, HIP events on its stream), the steady-iteration, dense-cost
+and Riccati-sweep rooflines, `secondary` (configs 3 and 4, the IL step) and
+`cpu_baseline` (the reference's CPU PyTorch op structure restated in fp32
+torch, oracle/torch_cpu.py, on the host cores).
 """
 import argparse
 import json
@@ -658,6 +662,58 @@ def profile_set(name, dev):
     print(json.dumps(out), flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, rank=0, world=1, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: what the last timed solve returned to its caller, one
+    DIR/<name>.npy per array (float32, as computed).  `arrays` maps a name to
+    (tensor, batch axis).  Above `limit` bytes in all (shared evenly by the
+    ranks) the same seeded sample of problems, in ascending order, is kept of
+    every array.  Files of rank r of N > 1 are named <name>_rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    B = next(t.shape[ax] for t, ax in arrays.values())
+    total = sum(t.numel() * t.element_size() for t, _ in arrays.values())
+    keep = None
+    if total > limit // world:
+        n_keep = max(1, int(B * (limit // world) / total))
+        keep = np.sort(np.random.RandomState(seed).choice(B, n_keep, replace=False))
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, (t, ax) in arrays.items():
+        if keep is not None:
+            t = t.index_select(ax, torch.as_tensor(keep, device=t.device))
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), t.detach().float().cpu().numpy())
+
+
+def headline(args, world, B, B_total, elapsed, ranks=None):
+    """The result line of a plain run: the headline figure from the timed steps
+    (--full adds the rooflines, `secondary` and `cpu_baseline` to it)."""
+    line = {
+        "metric": "iLQR iters/sec (whole node), batch=65536 cartpole T=25 at 1/2/4/8 MI355X",
+        "value": B_total * args.lqr_iter * args.steps / elapsed,
+        "unit": "problem-iters/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed * 1e3 / args.steps,
+        "ms_per_iteration": elapsed * 1e3 / (args.steps * args.lqr_iter),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (SURVEY.md §8(d) config 2 x_init, seed 0; cartpole get_true_obj cost materialised "
+                "per (t,b))",
+        "config": {"workload": "cartpole n=5 m=1 T=25, unconstrained iLQR, 65536 problems per GPU, "
+                               f"step = one whole-batch MPC solve of lqr_iter={args.lqr_iter} from u=0",
+                   "batch_per_gpu": B, "global_batch": B_total, "T": T_HORIZON, "lqr_iter": args.lqr_iter,
+                   "parallelism": f"batch-sharded x{world} (no collective)",
+                   "batch_iters_per_s": world * args.lqr_iter * args.steps / elapsed},
+    }
+    if ranks is not None:
+        line["ranks"] = ranks
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -669,8 +725,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--lqr-iter", type=int, default=10)
     ap.add_argument("--batch", type=int, default=B_PER_GPU, help="problems per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config 3/4 information lines")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the rooflines (runs of their own), "
+                         "configs 3 and 4 and the IL step (`secondary`) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the config 3/4 information lines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (best x, u, cost, du) as "
+                         "DIR/<name>.npy (float32; a seeded sample of the problems above 64 MB in all)")
     ap.add_argument("--kernels-only", action="store_true",
                     help="profiling mode: a few launches of the fused iteration and the sweep, no JSON line")
     ap.add_argument("--dump", default=None,
@@ -766,6 +829,21 @@ def main():
         os.makedirs(args.dump, exist_ok=True)
         torch.save({"rows": (lo, hi), "x": xb.cpu(), "u": ub.cpu(), "cost": sv.best_cost.cpu()},
                    os.path.join(args.dump, f"shard{rank}.pt"))
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last solve (ops.mpc_solve's return)
+        xb, ub = sv.gather_best()
+        dump_outputs(args.dump_outputs, {"x": (xb, 1), "u": (ub, 1), "cost": (sv.best_cost, 0),
+                                         "du": (sv.best_du, 0)}, rank, world)
+        del xb, ub
+
+    if not (args.full or args.kernels_only):
+        # a plain run: the headline figure alone
+        if rank == 0:
+            print(json.dumps(headline(args, world, B, B_total, elapsed, ranks)), flush=True)
+        if dist:
+            tdist.barrier()
+            tdist.destroy_process_group()
+        return
 
     # ---- roofline of the dominant kernel: the whole-solve launch
     # (k_mpc_solve_fixed + its finish, one dilqr_mpc_solve_fixed_f32 call = one
@@ -825,30 +903,12 @@ def main():
     if rank == 0 and args.kernels_only:
         print(json.dumps({"solve_ms": solve_ms, "iter_ms": iter_ms, "sweep_ms": sweep_ms}), flush=True)
     elif rank == 0:
-        value = B_total * args.lqr_iter * args.steps / elapsed
         achieved = solve_bytes / (solve_ms * 1e-3) / 1e9
         it_achieved = iter_bytes / (iter_ms * 1e-3) / 1e9
         sweep_gbs = sweep_bytes / (sweep_ms * 1e-3) / 1e9
-        line = {
-            "metric": "iLQR iters/sec (whole node), batch=65536 cartpole T=25 at 1/2/4/8 MI355X",
-            "value": value,
-            "unit": "problem-iters/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed * 1e3 / args.steps,
-            "ms_per_iteration": elapsed * 1e3 / (args.steps * args.lqr_iter),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (SURVEY.md §8(d) config 2 x_init, seed 0; cartpole get_true_obj cost materialised "
-                    "per (t,b))",
-            "config": {"workload": "cartpole n=5 m=1 T=25, unconstrained iLQR, 65536 problems per GPU, "
-                                   f"step = one whole-batch MPC solve of lqr_iter={args.lqr_iter} from u=0",
-                       "batch_per_gpu": B, "global_batch": B_total, "T": T_HORIZON, "lqr_iter": args.lqr_iter,
-                       "parallelism": f"batch-sharded x{world} (no collective)",
-                       "batch_iters_per_s": world * args.lqr_iter * args.steps / elapsed},
+        line = headline(args, world, B, B_total, elapsed, ranks)
+        value = line["value"]
+        line.update({
             "roofline": {"kernel": "k_mpc_solve_fixed<Cartpole,UNC,LDS gains> + k_mpc_fixed_finish (one whole "
                                    "fixed-count solve: begin + iteration 0 reading the caller's C + "
                                    f"{args.lqr_iter - 1} steady iterations; " + cost_path + ")",
@@ -875,9 +935,7 @@ def main():
                                  "bound": "hbm", "achieved": sweep_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                  "frac": sweep_gbs / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": sweep_bytes,
                                  "avg_launch_ms": sweep_ms},
-        }
-        if ranks is not None:
-            line["ranks"] = ranks
+        })
         if world == 1 and not args.no_secondary:
             line["secondary"] = secondary_configs(dev)
         if world == 1 and not args.no_cpu_baseline:

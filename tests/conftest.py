@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -24,8 +25,12 @@ def golden():
     cache = {}
 
     def load(name):
+        # name.npz plus name.part1.npz, ...: a set above 1 MiB is stored in parts (gen_golden.py save)
         if name not in cache:
-            cache[name] = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+            cache[name] = {}
+            for path in [os.path.join(GOLDEN, name + ".npz")] + sorted(
+                    glob.glob(os.path.join(GOLDEN, name + ".part*.npz"))):
+                cache[name].update(np.load(path))
         return cache[name]
 
     return load

@@ -21,6 +21,7 @@ Recipes follow SURVEY.md §8(c):
 Usage:  python tests/golden/gen_golden.py   (takes ~1-2 minutes on 8 cores)
 """
 import contextlib
+import glob
 import io
 import os
 import pickletools
@@ -78,10 +79,31 @@ def np_(t):
     return np.asarray(t)
 
 
+MAX_FILE_BYTES = 1 << 20       # no fixture file above 1 MiB
+
+
 def save(name, **arrs):
-    path = os.path.join(OUT, name + ".npz")
-    np.savez_compressed(path, **{k: np.asarray(v) for k, v in arrs.items()})
-    print(f"  wrote {name}.npz ({os.path.getsize(path)/1024:.1f} KiB)")
+    """name.npz; a set that compresses to more than MAX_FILE_BYTES is split, in
+    key order, into name.npz, name.part1.npz, ... (the tests' `golden` fixture
+    loads every part into one dict)."""
+    arrs = {k: np.asarray(v) for k, v in arrs.items()}
+    for old in glob.glob(os.path.join(OUT, name + ".part*.npz")):
+        os.remove(old)
+    parts = [list(arrs)]
+    while True:
+        paths = [os.path.join(OUT, name + (f".part{i}" if i else "") + ".npz") for i in range(len(parts))]
+        for path, keys in zip(paths, parts):
+            np.savez_compressed(path, **{k: arrs[k] for k in keys})
+        big = [i for i, path in enumerate(paths) if os.path.getsize(path) > MAX_FILE_BYTES and len(parts[i]) > 1]
+        if not big:
+            break
+        i = big[0]                  # halve the first oversized part by raw bytes, keeping the key order
+        keys = parts[i]
+        run = np.cumsum([arrs[k].nbytes for k in keys])
+        cut = min(max(int(np.searchsorted(run, run[-1] / 2)), 1), len(keys) - 1)
+        parts[i:i + 1] = [keys[:cut], keys[cut:]]
+    for path in paths:
+        print(f"  wrote {os.path.basename(path)} ({os.path.getsize(path)/1024:.1f} KiB)")
 
 
 def model(name):
@@ -343,9 +365,11 @@ def case_mpc_iterates():
     print("E'. mpc per-iteration entries")
     for dt in (torch.float64, torch.float32):
         with default_dtype(dt):
-            path = os.path.join(OUT, f"mpc_{tname(dt)}.npz")
-            with np.load(path) as old:
-                out = {k: old[k] for k in old.files}
+            out = {}
+            for path in [os.path.join(OUT, f"mpc_{tname(dt)}.npz")] + sorted(
+                    glob.glob(os.path.join(OUT, f"mpc_{tname(dt)}.part*.npz"))):
+                with np.load(path) as old:
+                    out.update({k: old[k] for k in old.files})
             for name in MPC_ITERATE_CASES:
                 for k in (1, 2, 3):
                     _, x, u, costs = run_mpc(name, dt, lqr_iter_override=k)

@@ -1,4 +1,4 @@
-"""Summarise tools/ab.sh lines of full bench.py runs (AB_CMD="bench.py --no-cpu-baseline"): headline, config 4, steady iteration, IL steps."""
+"""Summarise tools/ab.sh lines of full bench.py runs (AB_CMD="bench.py --full --no-cpu-baseline"): headline, config 4, steady iteration, IL steps."""
 import json,sys
 for line in sys.stdin:
     v, _, js = line.partition(' ')

@@ -13,7 +13,9 @@ for line in open(sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/ab.log"):
     except ValueError:
         continue
     if "ms_per_step" in d:
-        rows[v].append((d["ms_per_step"], d["roofline"]["avg_launch_ms"], d["riccati_roofline"]["avg_launch_ms"]))
+        # a plain bench line has the step time alone; --full lines carry the launch times
+        rows[v].append((d["ms_per_step"], d.get("roofline", {}).get("avg_launch_ms", 0.0),
+                        d.get("riccati_roofline", {}).get("avg_launch_ms", 0.0)))
     else:
         rows[v].append((d.get("iter_ms", 0.0), d.get("iter_ms", 0.0), d.get("sweep_ms", 0.0)))
 for v, r in sorted(rows.items()):

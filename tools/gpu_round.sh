@@ -18,14 +18,14 @@ if [[ "$STEPS" == *all* || "$STEPS" == *smoke* ]]; then
   echo "smoke rc=$rc"; tail -5 $OUT/smoke.log; [ $rc -eq 0 ] || exit $rc
 fi
 if [[ "$STEPS" == *all* || "$STEPS" == *bench* ]]; then
-  timeout -k 10 300 python bench.py ${BENCH_ARGS:-} > $OUT/bench.log 2>&1; rc=$?
+  timeout -k 10 300 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.log 2>&1; rc=$?
   echo "bench rc=$rc"; tail -3 $OUT/bench.log; [ $rc -eq 0 ] || exit $rc
 fi
 if [[ "$STEPS" == *all* || "$STEPS" == *prof* ]]; then
   R=$(pwd)
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof -o run --output-format csv -- \
-      python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $R/$OUT/prof.log 2>&1; rc=$?
+      python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $R/$OUT/prof.log 2>&1; rc=$?
   echo "rocprof rc=$rc"; tail -3 $R/$OUT/prof.log; [ $rc -eq 0 ] || exit $rc
   # the roofline kernel alone (bench --kernels-only: the steady-state fused
   # iteration's launches are exactly the ones bench.py times with HIP events)

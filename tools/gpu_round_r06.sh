@@ -22,14 +22,14 @@ if has smoke; then
   echo "smoke rc=$rc"; tail -2 $OUT/smoke.log; [ $rc -eq 0 ] || exit $rc
 fi
 if has bench; then
-  timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > $OUT/bench.log 2>&1; rc=$?
+  timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.log 2>&1; rc=$?
   echo "bench rc=$rc"; tail -c 600 $OUT/bench.log; echo; [ $rc -eq 0 ] || exit $rc
 fi
 if has prof; then
   R=$(pwd)
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof -o run --output-format csv -- \
-      python3 $R/bench.py --no-cpu-baseline > $R/$OUT/prof.log 2>&1; rc=$?
+      python3 $R/bench.py --full --no-cpu-baseline > $R/$OUT/prof.log 2>&1; rc=$?
   echo "rocprof rc=$rc"; [ $rc -eq 0 ] || exit $rc
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof_k -o run --output-format csv -- \
       python3 $R/bench.py --kernels-only > $R/$OUT/prof_k.log 2>&1; rc=$?

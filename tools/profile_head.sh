@@ -13,7 +13,7 @@ mkdir -p $OUT/stats
 make -C $R/differentiable-ilqr_amd -j16 > $OUT/build.log 2>&1 || { echo "build failed"; tail -20 $OUT/build.log; exit 1; }
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/stats/bench -o run --output-format csv -- \
-    python3 $R/bench.py > $OUT/stats/bench.log 2>&1
+    python3 $R/bench.py --full > $OUT/stats/bench.log 2>&1
 rc=$?; echo "stats bench rc=$rc"; tail -1 $OUT/stats/bench.log; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/stats/kern -o run --output-format csv -- \
     python3 $R/bench.py --kernels-only > $OUT/stats/kern.log 2>&1
