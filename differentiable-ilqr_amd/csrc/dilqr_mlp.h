@@ -1,0 +1,151 @@
+// dilqr_mlp.h — device model of the reference's NNDynamics with one hidden
+// layer (dynamics.py:15-130):  x' = W2 act(W1 [x;u] + b1) + b2  (+ x with
+// passthrough), act = sigmoid or relu, and its Jacobian as grad_input writes it
+// (dynamics.py:92-130):  W2 diag(act') W1  (+ I on the state block), act' =
+// a(1-a) for sigmoid, (a > 0) for relu.  No control clamp.
+//
+// Mapping: one row (problem) per lane.  The weights are the same for every
+// lane, so each lane walks the hidden units j = 0..H-1 with wave-uniform weight
+// addresses:  z_j = b1_j + W1_j . tau,  a_j = act(z_j),  o_i += W2_ij a_j,
+// J_ik += (W2_ij act'_j) W1_jk.  No activation is stored; the live state is the
+// n*d + n + d accumulators.  W1 [H,d], b1 [H], W2 [n,H], b2 [n] are torch's
+// nn.Linear layouts, read in place.
+//
+// Weight reads (both measured): by default through the constant
+// address space — the addresses are wave-uniform, so the compiler issues scalar
+// loads and the weights never occupy vector registers; with -DDILQR_MLP_LDS=1
+// each workgroup stages them once in LDS and every lane reads the same LDS
+// address (a broadcast).
+#pragma once
+#include "dilqr_device.h"
+
+namespace dilqr {
+
+constexpr int kMlpMaxHidden = DILQR_MLP_MAX_HIDDEN;
+
+#ifndef DILQR_MLP_LDS
+#define DILQR_MLP_LDS 0
+#endif
+
+// the model as the kernels receive it (by value, a kernel argument)
+struct MlpArg {
+  int H, passthrough;
+  const float *W1, *b1, *W2, *b2;
+};
+
+#if DILQR_MLP_LDS
+typedef const float* MlpW;
+// floats a workgroup stages: W1, b1, W2, b2
+inline size_t mlp_lds_bytes(int n, int m, int H) { return sizeof(float) * ((size_t)H * (n + m) + H + (size_t)n * H + n); }
+#else
+typedef const __attribute__((address_space(4))) float* MlpW;
+inline size_t mlp_lds_bytes(int, int, int) { return 0; }
+#endif
+
+template <int N_, int M_, int ACT>
+struct Mlp {
+  static constexpr int N = N_, M = M_, D = N_ + M_;
+  static constexpr bool kForwardJacobian = true;   // forward_jacobian(): one walk over the hidden units
+  using Arg = MlpArg;
+  int H;
+  bool pt;
+  MlpW W1, b1, W2, b2;
+
+  DEV void load(const MlpArg& a) {
+    H = a.H;
+    pt = a.passthrough != 0;
+#if DILQR_MLP_LDS
+    extern __shared__ float mlp_lds[];
+    float* s = mlp_lds;
+    // the lanes still active copy (a tail workgroup has fewer than 64): lane of
+    // rank r among them takes elements r, r + active, ...
+    const unsigned long long act = __ballot(1);
+    const int lane = threadIdx.x & 63;
+    const int r = __popcll(act & ((1ull << lane) - 1ull)), na = __popcll(act);
+    const float* src[4] = {a.W1, a.b1, a.W2, a.b2};
+    const int cnt[4] = {H * D, H, N * H, N};
+    float* dst[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      dst[q] = s;
+      for (int i = r; i < cnt[q]; i += na) s[i] = src[q][i];
+      s += cnt[q];
+    }
+    __syncthreads();
+    W1 = dst[0]; b1 = dst[1]; W2 = dst[2]; b2 = dst[3];
+#else
+    W1 = (MlpW)a.W1; b1 = (MlpW)a.b1; W2 = (MlpW)a.W2; b2 = (MlpW)a.b2;
+#endif
+  }
+
+  // a = act(z), g = act'(z) as grad_input forms it from a (dynamics.py:107-118)
+  static DEV void activate(float z, float& a, float& g) {
+    if constexpr (ACT == DILQR_MLP_RELU) {
+      a = fmaxf(z, 0.f);
+      g = a > 0.f ? 1.f : 0.f;
+    } else {
+      a = vrcp(1.0f + __expf(-z));
+      g = a * (1.0f - a);
+    }
+  }
+
+  template <bool FWD, bool JAC>
+  DEV void walk(const float (&x)[N], const float (&u)[M], float (*o)[N], float (*J)[N][D]) const {
+    float tau[D], acc[N], Jr[N][D];
+#pragma unroll
+    for (int i = 0; i < N; ++i) tau[i] = x[i];
+#pragma unroll
+    for (int a = 0; a < M; ++a) tau[N + a] = u[a];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      acc[i] = FWD ? b2[i] : 0.f;
+#pragma unroll
+      for (int k = 0; k < D; ++k) Jr[i][k] = 0.f;
+    }
+#pragma unroll 4
+    for (int j = 0; j < H; ++j) {
+      float w[D];
+#pragma unroll
+      for (int k = 0; k < D; ++k) w[k] = W1[j * D + k];
+      float z = b1[j];
+#pragma unroll
+      for (int k = 0; k < D; ++k) z += w[k] * tau[k];
+      float a, g;
+      activate(z, a, g);
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const float w2 = W2[i * H + j];
+        if constexpr (FWD) acc[i] += w2 * a;
+        if constexpr (JAC) {
+          const float s = w2 * g;
+#pragma unroll
+          for (int k = 0; k < D; ++k) Jr[i][k] += s * w[k];
+        }
+      }
+    }
+    if constexpr (FWD) {
+#pragma unroll
+      for (int i = 0; i < N; ++i) (*o)[i] = pt ? acc[i] + x[i] : acc[i];
+    }
+    if constexpr (JAC) {
+#pragma unroll
+      for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int k = 0; k < D; ++k) (*J)[i][k] = (pt && i == k) ? Jr[i][k] + 1.0f : Jr[i][k];
+    }
+  }
+
+  // dynamics.py:66-90
+  DEV void forward(const float (&x)[N], const float (&u)[M], float (&o)[N]) const {
+    walk<true, false>(x, u, &o, nullptr);
+  }
+  // dynamics.py:92-130: [R S]
+  DEV void jacobian(const float (&x)[N], const float (&u)[M], float (&J)[N][D]) const {
+    walk<false, true>(x, u, nullptr, &J);
+  }
+  DEV void forward_jacobian(const float (&x)[N], const float (&u)[M], float (&o)[N], float (&J)[N][D]) const {
+    walk<true, true>(x, u, &o, &J);
+  }
+};
+
+}  // namespace dilqr

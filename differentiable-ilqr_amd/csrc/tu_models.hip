@@ -1,23 +1,9 @@
 // tu_models.hip — dynamics, Jacobians, rollouts, linearisation, standalone pnqp,
 // the quirk du-norm; the library version and build id.
 #include "dilqr_common.h"
+#include "dilqr_model_kernels.h"   // k_dynamics, k_linear_dyn, k_rollout, k_linearize
 
 namespace dilqr {
-
-// ============================================================ model kernels
-template <class Model>
-__global__ void __launch_bounds__(kBlock) k_dynamics(int N, const float* __restrict__ theta,
-                                                     const float* __restrict__ x, const float* __restrict__ u,
-                                                     float* __restrict__ out) {
-  constexpr int n = Model::N, m = Model::M;
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  Model md; md.load(theta);
-  float xi[n], ui[m], o[n];
-  ld(xi, x + (size_t)i * n); ld(ui, u + (size_t)i * m);
-  md.forward(xi, ui, o);
-  st(out + (size_t)i * n, o);
-}
 
 // Vector-Jacobian product of forward() (the sysid loss's backward,
 // il_exp.py:338-347, which the reference gets from autograd): per row,
@@ -62,42 +48,6 @@ __global__ void __launch_bounds__(kBlock) k_dynamics_vjp(int N, const float* __r
   if (gu) st(gu + (size_t)i * m, gui);
 }
 
-template <class Model>
-__global__ void __launch_bounds__(kBlock) k_linear_dyn(int N, const float* __restrict__ theta,
-                                                       const float* __restrict__ x, const float* __restrict__ u,
-                                                       float* __restrict__ Dout) {
-  constexpr int n = Model::N, m = Model::M, d = n + m;
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  Model md; md.load(theta);
-  float xi[n], ui[m], D[n][d];
-  ld(xi, x + (size_t)i * n); ld(ui, u + (size_t)i * m);
-  md.jacobian(xi, ui, D);
-  st2(Dout + (size_t)i * n * d, D);
-}
-
-// util.get_traj (util.py:104-127)
-template <class Model>
-__global__ void __launch_bounds__(kBlock) k_rollout(int T, int B, const float* __restrict__ theta,
-                                                    const float* __restrict__ x_init, const float* __restrict__ u,
-                                                    float* __restrict__ x_out) {
-  constexpr int n = Model::N, m = Model::M;
-  int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  Model md; md.load(theta);
-  float xt[n];
-  ld(xt, x_init + (size_t)b * n);
-  st(x_out + (size_t)b * n, xt);
-  for (int t = 0; t < T - 1; ++t) {
-    float ut[m], xn[n];
-    ld(ut, u + ((size_t)t * B + b) * m);
-    md.forward(xt, ut, xn);
-#pragma unroll
-    for (int i = 0; i < n; ++i) xt[i] = xn[i];
-    st(x_out + ((size_t)(t + 1) * B + b) * n, xt);
-  }
-}
-
 // LinDx rollout: x_{t+1} = F_t [x_t;u_t] + f_t
 template <int n, int m>
 __global__ void __launch_bounds__(kBlock) k_rollout_lin(int T, int B, const float* __restrict__ F,
@@ -131,32 +81,6 @@ __global__ void __launch_bounds__(kBlock) k_rollout_lin(int T, int B, const floa
     for (int i = 0; i < n; ++i) xt[i] = xn[i];
     st(x_out + ((size_t)(t + 1) * B + b) * n, xt);
   }
-}
-
-// MPC.linearize_dynamics ANALYTIC (mpc_explicit.py:516-546)
-template <class Model>
-__global__ void __launch_bounds__(kBlock) k_linearize(int T, int B, const float* __restrict__ theta,
-                                                      const float* __restrict__ x, const float* __restrict__ u,
-                                                      float* __restrict__ F, float* __restrict__ f) {
-  constexpr int n = Model::N, m = Model::M, d = n + m;
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)(T - 1) * B) return;
-  Model md; md.load(theta);
-  float xi[n], ui[m], D[n][d], xn[n], fo[n];
-  ld(xi, x + (size_t)i * n); ld(ui, u + (size_t)i * m);
-  md.forward(xi, ui, xn);
-  md.jacobian(xi, ui, D);
-#pragma unroll
-  for (int r = 0; r < n; ++r) {
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < n; ++j) s += D[r][j] * xi[j];
-#pragma unroll
-    for (int j = 0; j < m; ++j) s += D[r][n + j] * ui[j];
-    fo[r] = xn[r] - s;
-  }
-  st2(F + (size_t)i * n * d, D);
-  st(f + (size_t)i * n, fo);
 }
 
 // ============================================================ quirk du-norm
@@ -205,7 +129,7 @@ using namespace dilqr;
 
 extern "C" {
 
-int dilqr_version(void) { return 9; }
+int dilqr_version(void) { return 10; }
 
 // hash of csrc/ + include/dilqr.h at build time (Makefile); _native checks it
 // against the tree so a stale prebuilt library cannot be loaded silently

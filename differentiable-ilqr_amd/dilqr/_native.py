@@ -14,10 +14,15 @@ import torch  # noqa: F401  (must be imported first: libdilqr.so then binds to t
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DILQR_LIB", os.path.join(_HERE, "libdilqr.so"))
-ABI_VERSION = 9
+ABI_VERSION = 10
 _PKG = os.path.dirname(_HERE)          # differentiable-ilqr_amd/ (the Makefile's directory)
 
 MODEL_LINDX, MODEL_PENDULUM, MODEL_CARTPOLE, MODEL_ROCKET, MODEL_PENDULUM_COMPLEX = 0, 1, 2, 3, 4
+MODEL_MLP = 5          # a one-hidden-layer network, described by an Mlp (the dilqr_mlp_* entry points)
+MLP_SIGMOID, MLP_RELU = 0, 1
+MLP_MAX_HIDDEN = 256   # DILQR_MLP_MAX_HIDDEN
+# (n, m) the one-lane-per-problem kernels are compiled for (csrc/dilqr_common.h DILQR_FOR_EACH_SHAPE)
+LANE_SHAPES = ((3, 1), (5, 1), (4, 3), (4, 1), (2, 1), (4, 2), (6, 2), (6, 1))
 BOUNDS_NONE, BOUNDS_SCALAR, BOUNDS_TENSOR = 0, 1, 2
 SOLVE_INV, SOLVE_CHOL = 0, 1
 ERRORS = {1: "unsupported shape/model", 2: "invalid argument", 3: "unsupported option combination"}
@@ -26,6 +31,12 @@ ERRORS = {1: "unsupported shape/model", 2: "invalid argument", 3: "unsupported o
 class Bounds(ctypes.Structure):
     _fields_ = [("mode", ctypes.c_int), ("lo", ctypes.c_float), ("hi", ctypes.c_float),
                 ("lo_t", ctypes.c_void_p), ("hi_t", ctypes.c_void_p)]
+
+
+class Mlp(ctypes.Structure):
+    """dilqr_mlp: a one-hidden-layer network's sizes and weight pointers (include/dilqr.h)."""
+    _fields_ = [("n_hidden", ctypes.c_int), ("activation", ctypes.c_int), ("passthrough", ctypes.c_int),
+                ("W1", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("W2", ctypes.c_void_p), ("b2", ctypes.c_void_p)]
 
 
 CTRL_INTS = 8          # sizeof(dilqr_mpc_ctrl) / 4
@@ -80,6 +91,12 @@ SIGNATURES = {
                               _vp], _i),
     "dilqr_implicit_backward_f32": ([_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Bounds, _vp, _vp, _vp,
                                      _vp, _vp], _i),
+    "dilqr_mlp_dynamics_f32": ([_i, _i, _i, Mlp, _vp, _vp, _vp, _vp], _i),
+    "dilqr_mlp_linear_dyn_f32": ([_i, _i, _i, Mlp, _vp, _vp, _vp, _vp], _i),
+    "dilqr_mlp_rollout_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp], _i),
+    "dilqr_mlp_linearize_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp, _vp], _i),
+    "dilqr_mlp_lqr_forward_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Bounds, _vp, _f, _i, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp], _i),
 }
 
 _lib = None

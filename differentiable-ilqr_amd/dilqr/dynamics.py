@@ -5,7 +5,11 @@ They are plain torch Modules — evaluated by torch on the GPU — with the
 reference's constructor arguments, parameter layout (so its state dicts load)
 and `grad_input` Jacobians.  The fused HIP kernels never see them: the MPC
 routes any dynamics other than the env_dx models through dilqr.generic, whose
-Riccati sweeps are the HIP kernel.
+Riccati sweeps are the HIP kernel.  An NNDynamics with one hidden layer
+(sigmoid or relu) also has a device model (`device_model`, csrc/dilqr_mlp.h):
+dilqr.generic then runs its rollouts, ANALYTIC linearisation, line search and
+whole solves through the HIP MLP kernels, which read the module's weights in
+place; gradients into the weights still go through torch (final_step).
 """
 import torch
 import torch.nn.functional as Fn
@@ -53,6 +57,30 @@ class NNDynamics(nn.Module):
         if self.passthrough:
             z = z + x
         return z.squeeze(0) if x_dim == 1 else z
+
+    def device_model(self, like):
+        """The network as the HIP MLP kernels take it (ops.MlpModel: sizes, flags
+        and pointers to this module's own parameter storage — no copy, so an
+        optimiser step is seen by the next solve), or None when the module is
+        outside their envelope: more than one hidden layer, elu, a hidden width
+        above N.MLP_MAX_HIDDEN, an (n, m) the one-lane kernels are not compiled
+        for, parameters that are not fp32 / contiguous / 16-byte aligned, or
+        parameters on another device than `like`."""
+        from . import _native as N
+        from . import ops
+        if len(self.fcs) != 2 or self.activation not in ("sigmoid", "relu"):
+            return None
+        W1, b1, W2, b2 = self.fcs[0].weight, self.fcs[0].bias, self.fcs[1].weight, self.fcs[1].bias
+        H, d = W1.shape
+        n = W2.shape[0]
+        if (n, d - n) not in N.LANE_SHAPES or not 1 <= H <= N.MLP_MAX_HIDDEN:
+            return None
+        for p in (W1, b1, W2, b2):
+            if p is None or p.dtype != torch.float32 or not p.is_contiguous() or p.device != like.device \
+                    or p.data_ptr() % 16:
+                return None
+        act = N.MLP_SIGMOID if self.activation == "sigmoid" else N.MLP_RELU
+        return ops.MlpModel(n, d - n, act, self.passthrough, W1.detach(), b1.detach(), W2.detach(), b2.detach())
 
     def grad_input(self, x, u):
         """dynamics.py:92-130: R = d x'/d x, S = d x'/d u from the weights and the

@@ -12,6 +12,9 @@ whole horizon wherever the reference loops over t, and every Riccati sweep
 follows lqr_step_explicit.py:166-263 with per-problem step sizes (the
 reference's `torch.diag(alphas).mm(kt)` is O(B^2); here it is a broadcast),
 the best-iterate bookkeeping and stop rule follow mpc_explicit.py:262-299.
+One Module is not run by torch: an NNDynamics with a device model (one hidden
+layer, sigmoid or relu; NNDynamics.device_model) goes through the HIP MLP
+kernels — see DEVICE_MLP below.
 
 Nothing here is on the HIP hot path of the headline: those solves go through
 ops.mpc_solve.  This module exists so that a user of the reference with any
@@ -49,6 +52,36 @@ def quad_stage_cost(tau, C, c):
     return 0.5 * bquad(tau, C) + bdot(tau, c)
 
 
+# ---------------------------------------------------------------- the device MLP route
+# A dynamics Module with a device model (NNDynamics.device_model: one hidden
+# layer, sigmoid/relu, within the kernels' shapes) runs its rollouts, its
+# ANALYTIC linearisation, its line search and, for a quadratic cost without
+# slew-rate penalty or delta_u, the whole solve through the HIP MLP kernels
+# (csrc/tu_mlp.hip).  False restores the torch loop everywhere (tests and
+# tools/bench_nn_mpc.py run both on the same inputs).
+DEVICE_MLP = True
+
+
+def device_mlp(dynamics, like):
+    """dynamics' ops.MlpModel for tensors like `like` (a GPU fp32 tensor), or None."""
+    if not DEVICE_MLP or isinstance(dynamics, LinDx) or not like.is_cuda or like.dtype != torch.float32:
+        return None
+    make = getattr(dynamics, "device_model", None)
+    return None if make is None else make(like)
+
+
+def device_solve_ok(mpc, cost, dx, x_init):
+    """The MlpModel when the whole solve can run on device (ops.mpc_solve_unfused
+    on the MLP model): a device model, a quadratic cost, the ANALYTIC
+    linearisation, no slew-rate penalty, no delta_u, not verbose (the torch
+    loop's table prints the pnqp count, which the device loop does not form)."""
+    from .mpc_explicit import GradMethods
+    if not (isinstance(cost, QuadCost) and mpc.grad_method == GradMethods.ANALYTIC
+            and mpc.slew_rate_penalty is None and mpc.delta_u is None and getattr(mpc, "verbose", 0) <= 0):
+        return None
+    return device_mlp(dx, x_init)
+
+
 # ---------------------------------------------------------------- dynamics / cost wrappers
 class CtrlPassthroughDynamics(torch.nn.Module):
     """dynamics.py:133-156: state [u_{t-1}; x_t] -> [u_t; f(x_t, u_t)]."""
@@ -81,6 +114,9 @@ class SlewRateCost(torch.nn.Module):
 
 def rollout(T, u, x_init, dynamics):
     """util.get_traj (util.py:104-127)."""
+    mlp = device_mlp(dynamics, x_init)
+    if mlp is not None:
+        return ops.mlp_rollout(mlp, x_init.detach(), u.detach())
     x = [x_init.detach()]
     with torch.no_grad():
         for t in range(T - 1):
@@ -120,6 +156,11 @@ def linearize(mpc, x, u, dynamics, diff):
     if gm == GradMethods.ANALYTIC and mid is not None and not diff:
         # the env_dx models: the HIP linearisation (get_linear_dyn, unclamped u)
         return ops.linearize(mid, ops.theta_of(dynamics, x), x.detach(), u.detach())
+    if gm == GradMethods.ANALYTIC and not diff and mid is None and hasattr(dynamics, "grad_input"):
+        mlp = device_mlp(dynamics, x)
+        if mlp is not None:
+            # the network: value and grad_input's [R S] of every row in one kernel
+            return ops.mlp_linearize(mlp, x.detach(), u.detach())
     xs = x[:-1].detach().reshape(-1, n)
     us = u[:-1].detach().reshape(-1, m)
     if gm == GradMethods.ANALYTIC:
@@ -237,6 +278,20 @@ def lqr_step_forward(T, n, m, x_init, C, c, F, x, u, true_cost, true_dynamics, u
     else:
         K, k, nqp = ops.lqr_backward(Cd, cd, Fd, n, m, x=xd, u=ud, u_lower=lo, u_upper=hi,
                                      u_zero_I=zI if lo is None else None, qp_total=extras and lo is not None)
+    mlp = None
+    if isinstance(true_cost, QuadCost) and delta_u is None and tuple(true_cost.C.shape) == (T, B, n + m, n + m) \
+            and tuple(true_cost.c.shape) == (T, B, n + m):
+        mlp = device_mlp(true_dynamics, x)
+    if mlp is not None:
+        # the line search on device (k_lqr_forward on the MLP model): the same
+        # per-problem rule; du_sq is the first pass's, alphas the last pass's
+        new_x, new_u, cur_cost, du_sq, alphas = ops.lqr_forward(
+            mlp, None, x_init.detach(), true_cost.C.detach(), true_cost.c.detach(), xd, ud, K, k, u_lower=lo,
+            u_upper=hi, u_zero_I=zI, linesearch_decay=decay, max_linesearch_iter=max_ls)
+        full_du_norm = ops.quirk_norm(du_sq)
+        if extras:
+            return new_x, new_u, cur_cost, full_du_norm, alphas, (nqp if isinstance(nqp, int) else 0)
+        return new_x, new_u, cur_cost, full_du_norm
     old_cost = traj_cost(T, x, u, true_cost)
     alphas = torch.ones(B, device=x.device)
     cur_cost, full_du_norm = None, None
@@ -350,6 +405,19 @@ def solve(mpc, x_init, cost, dx, n_batch):
     full_du_norm), all detached."""
     T, n, m = mpc.T, mpc.n_state, mpc.n_ctrl
     dev = x_init.device
+    mlp = device_solve_ok(mpc, cost, dx, x_init)
+    if mlp is not None and (mlp.n, mlp.m) == (n, m):
+        # the whole loop on device: rollout, linearise, sweep, line search and the
+        # best-iterate / stop rule, four launches per iteration, no host poll
+        # between them (ops.mpc_solve_unfused on the MLP model)
+        with torch.no_grad():
+            ws = ops.mpc_solve_unfused(
+                mlp, None, x_init.detach(), cost.C.detach().contiguous(), cost.c.detach().contiguous(), T,
+                u_init=mpc.u_init, u_lower=mpc.u_lower, u_upper=mpc.u_upper, lqr_iter=mpc.lqr_iter, eps=mpc.eps,
+                linesearch_decay=mpc.linesearch_decay, max_linesearch_iter=mpc.max_linesearch_iter,
+                not_improved_lim=mpc.not_improved_lim, best_cost_eps=mpc.best_cost_eps,
+                u_zero_I=getattr(mpc, "u_zero_I", None))
+        return ws.best_x, ws.best_u, ws.best_cost, ws.best_du
     if mpc.u_init is None:
         u = torch.zeros(T, n_batch, m, device=dev, dtype=x_init.dtype)
     else:

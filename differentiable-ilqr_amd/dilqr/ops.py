@@ -43,6 +43,101 @@ def theta_of(dx, like):
     return dx._theta(like)
 
 
+class MlpModel:
+    """A one-hidden-layer network as the dilqr_mlp_* entry points take it: the
+    dilqr_mlp descriptor (sizes, flags, raw pointers into the module's own
+    parameter storage: nothing is copied) plus (n, m) and the tensors that keep
+    the pointers alive.  Built by NNDynamics.device_model; passed to
+    lqr_forward / mpc_solve_unfused in place of (model_id, theta)."""
+    model_id = N.MODEL_MLP
+
+    def __init__(self, n, m, activation, passthrough, W1, b1, W2, b2):
+        H = W1.shape[0]
+        if (n, m) not in N.LANE_SHAPES or not 1 <= H <= N.MLP_MAX_HIDDEN:
+            raise ValueError(f"dilqr: no MLP kernels for (n, m) = {(n, m)}, H = {H}")
+        if (tuple(W1.shape), tuple(b1.shape), tuple(W2.shape), tuple(b2.shape)) != ((H, n + m), (H,), (n, H), (n,)):
+            raise ValueError("dilqr: MLP weights must be W1 [H,n+m], b1 [H], W2 [n,H], b2 [n]")
+        for t in (W1, b1, W2, b2):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != W1.device or t.data_ptr() % 16:
+                raise ValueError("dilqr: MLP weights must be fp32, contiguous, 16-byte aligned, on one device")
+        self.n, self.m, self.H, self.device = n, m, H, W1.device
+        self.tensors = (W1, b1, W2, b2)
+        self.desc = N.Mlp(H, int(activation), int(bool(passthrough)), *(t.data_ptr() for t in self.tensors))
+
+    def check(self, x, u):
+        """x [..., n], u [..., m] on the weights' device (the kernels index rows by n and m)."""
+        if x.shape[-1] != self.n or u.shape[-1] != self.m or x.shape[:-1] != u.shape[:-1]:
+            raise ValueError(f"dilqr: MLP model is (n, m) = {(self.n, self.m)}; got x {tuple(x.shape)}, "
+                             f"u {tuple(u.shape)}")
+        if x.device != self.device or u.device != self.device:
+            raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
+
+
+def _mlp(model_id, theta):
+    """The MlpModel when (model_id, theta) names one: the descriptor itself in
+    place of model_id, or MODEL_MLP with the descriptor as theta."""
+    if isinstance(model_id, MlpModel):
+        return model_id
+    if model_id == N.MODEL_MLP:
+        if not isinstance(theta, MlpModel):
+            raise TypeError("dilqr: MODEL_MLP needs an MlpModel (NNDynamics.device_model) as theta")
+        return theta
+    return None
+
+
+def _al16(t):
+    """t, or a copy when t is a view that does not start on a 16-byte boundary
+    (a row block of a larger tensor: the C-ABI takes aligned pointers only)."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def mlp_dynamics(mlp, x, u):
+    """NNDynamics.forward (dynamics.py:66-90) for rows x [N,n], u [N,m]."""
+    x, u = _al16(_f32(x)), _al16(_f32(u))
+    mlp.check(x, u)
+    rows = x.shape[0]
+    out = torch.empty(rows, mlp.n, device=x.device)
+    N.call("dilqr_mlp_dynamics_f32", mlp.n, mlp.m, rows, mlp.desc, N.ptr(x), N.ptr(u), N.ptr(out),
+           N.stream(x.device))
+    return out
+
+
+def mlp_linear_dyn(mlp, x, u):
+    """NNDynamics.grad_input (dynamics.py:92-130) as D = [R S], [N,n,n+m]."""
+    x, u = _al16(_f32(x)), _al16(_f32(u))
+    mlp.check(x, u)
+    rows = x.shape[0]
+    D = torch.empty(rows, mlp.n, mlp.n + mlp.m, device=x.device)
+    N.call("dilqr_mlp_linear_dyn_f32", mlp.n, mlp.m, rows, mlp.desc, N.ptr(x), N.ptr(u), N.ptr(D),
+           N.stream(x.device))
+    return D
+
+
+def mlp_rollout(mlp, x_init, u):
+    """util.get_traj (util.py:104-127) with the network: x [T,B,n]."""
+    T, B, _ = u.shape
+    x_init, u = _al16(_f32(x_init)), _al16(_f32(u))
+    mlp.check(x_init, u[0])
+    x = torch.empty(T, B, mlp.n, device=u.device)
+    N.call("dilqr_mlp_rollout_f32", mlp.n, mlp.m, T, B, mlp.desc, N.ptr(x_init), N.ptr(u), N.ptr(x),
+           N.stream(u.device))
+    return x
+
+
+def mlp_linearize(mlp, x, u):
+    """MPC.linearize_dynamics ANALYTIC with grad_input (mpc.py:494-519):
+    F [T-1,B,n,n+m], f [T-1,B,n] (empty, and nothing launched, at T = 1)."""
+    T, B, n = x.shape
+    x, u = _al16(_f32(x)), _al16(_f32(u))
+    mlp.check(x, u)
+    F = torch.empty(max(T - 1, 0), B, n, n + mlp.m, device=x.device)
+    f = torch.empty(max(T - 1, 0), B, n, device=x.device)
+    if T > 1 and B > 0:
+        N.call("dilqr_mlp_linearize_f32", mlp.n, mlp.m, T, B, mlp.desc, N.ptr(x), N.ptr(u), N.ptr(F), N.ptr(f),
+               N.stream(x.device))
+    return F, f
+
+
 def rollout(model_id, theta, x_init, u, F=None, f=None):
     """util.get_traj (util.py:104-127)."""
     T, B, m = u.shape
@@ -137,7 +232,9 @@ def delta_u_rollout_bounds(u_lower, u_upper, u, delta_u):
 def lqr_forward(model_id, theta, x_init, C, c, x, u, K, k, F=None, f=None, u_lower=None, u_upper=None,
                 u_zero_I=None, linesearch_decay=0.2, max_linesearch_iter=10):
     """lqr_forward (lqr_step_explicit.py:166-263): returns new_x, new_u, costs [B],
-    du_sq [T,m,B] (first pass), alphas [B] (final pass)."""
+    du_sq [T,m,B] (first pass), alphas [B] (final pass).  An MlpModel in place
+    of model_id (theta then ignored), or MODEL_MLP with it as theta, rolls out
+    the network (dilqr_mlp_lqr_forward_f32)."""
     T, B, n = x.shape
     m = u.shape[2]
     x_init, C, c, x, u, K, k, F, f = map(_f32, (x_init, C, c, x, u, K, k, F, f))
@@ -147,6 +244,19 @@ def lqr_forward(model_id, theta, x_init, C, c, x, u, K, k, F=None, f=None, u_low
     nx, nu = torch.empty_like(x), torch.empty_like(u)
     cost, alpha = torch.empty(B, device=dev), torch.empty(B, device=dev)
     du_sq = torch.empty(T, m, B, device=dev)
+    mlp = _mlp(model_id, theta)
+    if mlp is not None:
+        mlp.check(x, u)
+        d = n + m
+        if (tuple(x_init.shape), tuple(C.shape), tuple(c.shape), tuple(K.shape), tuple(k.shape)) != (
+                (B, n), (T, B, d, d), (T, B, d), (T, B, m, n), (T, B, m)):
+            raise ValueError("dilqr: lqr_forward operands must be x_init [B,n], C [T,B,d,d], c [T,B,d], "
+                             "K [T,B,m,n], k [T,B,m]")
+        N.call("dilqr_mlp_lqr_forward_f32", n, m, T, B, mlp.desc, N.ptr(x_init), N.ptr(C), N.ptr(c), N.ptr(x),
+               N.ptr(u), N.ptr(K), N.ptr(k), bounds, N.ptr(zI), float(linesearch_decay), int(max_linesearch_iter),
+               N.ptr(nx), N.ptr(nu), N.ptr(cost), N.ptr(du_sq), N.ptr(alpha), None, N.stream(dev))
+        del keep
+        return nx, nu, cost, du_sq, alpha
     N.call("dilqr_lqr_forward_f32", model_id, n, m, T, B, N.ptr(theta), N.ptr(F), N.ptr(f), N.ptr(x_init),
            N.ptr(C), N.ptr(c), N.ptr(x), N.ptr(u), N.ptr(K), N.ptr(k), bounds, N.ptr(zI),
            float(linesearch_decay), int(max_linesearch_iter), N.ptr(nx), N.ptr(nu), N.ptr(cost), N.ptr(du_sq),
@@ -543,7 +653,8 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
     iteration.  u_zero_I [T,B,m] (bool): controls held at zero — the sweep's
     masked solve when unconstrained (lqr_step_explicit.py:98-129; with bounds
     the reference's pnqp branch ignores the mask) and zeroed in every rollout
-    before the clamp (199-200).
+    before the clamp (199-200).  An MlpModel (NNDynamics.device_model) in place
+    of model_id, or MODEL_MLP with it as theta, runs the loop on the network.
 
     The host polls the stop flag every `check_every` iterations: up to
     check_every - 1 iterations after the stop rule fired still run their
@@ -554,6 +665,16 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
     m = C.shape[-1] - n
     dev = x_init.device
     x_init, C, c, F, f = _f32(x_init), _f32(C), _f32(c), _f32(F), _f32(f)
+    mlp = _mlp(model_id, theta)
+    if mlp is not None:
+        # the network: the same four launches per iteration through the
+        # dilqr_mlp_* entry points (rollout, linearise, line search)
+        if (mlp.n, mlp.m) != (n, m) or tuple(C.shape) != (T, B, n + m, n + m) or tuple(c.shape) != (T, B, n + m):
+            raise ValueError(f"dilqr: MLP model is (n, m) = {(mlp.n, mlp.m)}; got x_init {tuple(x_init.shape)}, "
+                             f"C {tuple(C.shape)}, c {tuple(c.shape)} at T = {T}")
+        if x_init.device != mlp.device:
+            raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
+        model_id = N.MODEL_MLP
     ws = MPCWorkspace(T, B, n, m, dev)
     if u_init is None:
         ws.ua.zero_()
@@ -564,8 +685,11 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
         ws.ua.copy_(u0)
     s = N.stream(dev)
     zI = zero_mask(u_zero_I, T, B, m, dev)
-    N.call("dilqr_rollout_f32", model_id, n, m, T, B, N.ptr(theta), N.ptr(F), N.ptr(f), N.ptr(x_init),
-           N.ptr(ws.ua), N.ptr(ws.xa), s)
+    if mlp is not None:
+        N.call("dilqr_mlp_rollout_f32", n, m, T, B, mlp.desc, N.ptr(x_init), N.ptr(ws.ua), N.ptr(ws.xa), s)
+    else:
+        N.call("dilqr_rollout_f32", model_id, n, m, T, B, N.ptr(theta), N.ptr(F), N.ptr(f), N.ptr(x_init),
+               N.ptr(ws.ua), N.ptr(ws.xa), s)
     stats = None
     if verbose > 0:                        # the table rows, reduced on the stream (util.print_solve_log)
         stats = torch.zeros(max(lqr_iter, 1), 3, device=dev)
@@ -574,6 +698,8 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
     for i in range(lqr_iter):
         if model_id == N.MODEL_LINDX:
             Fi, fi = F, f
+        elif mlp is not None:
+            Fi, fi = mlp_linearize(mlp, ws.xa, ws.ua)
         else:
             Fi, fi = linearize(model_id, theta, ws.xa, ws.ua)
         K, k, _ = lqr_backward(C, c, Fi, n, m, x=ws.xa, u=ws.ua, u_lower=u_lower, u_upper=u_upper,
@@ -581,11 +707,18 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
         bounds, keep = N.make_bounds(u_lower, u_upper)
         # from iteration 1 the old cost is the previous line search's value for
         # the accepted candidate (ws.cost), as the fused MPC kernel takes it
-        prev = (N.ptr(ws.cost) if i > 0 and model_id in (N.MODEL_PENDULUM, N.MODEL_CARTPOLE) else None)
-        N.call("dilqr_lqr_forward_f32", model_id, n, m, T, B, N.ptr(theta), N.ptr(F), N.ptr(f),
-               N.ptr(x_init), N.ptr(C), N.ptr(c), N.ptr(ws.xa), N.ptr(ws.ua), N.ptr(K), N.ptr(k), bounds, N.ptr(zI),
-               float(linesearch_decay), int(max_linesearch_iter), N.ptr(ws.xb), N.ptr(ws.ub), N.ptr(ws.cost),
-               N.ptr(ws.du_sq), N.ptr(ws.alpha), prev, s)
+        prev = (N.ptr(ws.cost) if i > 0 and model_id in (N.MODEL_PENDULUM, N.MODEL_CARTPOLE, N.MODEL_MLP)
+                else None)
+        if mlp is not None:
+            N.call("dilqr_mlp_lqr_forward_f32", n, m, T, B, mlp.desc, N.ptr(x_init), N.ptr(C), N.ptr(c),
+                   N.ptr(ws.xa), N.ptr(ws.ua), N.ptr(K), N.ptr(k), bounds, N.ptr(zI), float(linesearch_decay),
+                   int(max_linesearch_iter), N.ptr(ws.xb), N.ptr(ws.ub), N.ptr(ws.cost), N.ptr(ws.du_sq),
+                   N.ptr(ws.alpha), prev, s)
+        else:
+            N.call("dilqr_lqr_forward_f32", model_id, n, m, T, B, N.ptr(theta), N.ptr(F), N.ptr(f),
+                   N.ptr(x_init), N.ptr(C), N.ptr(c), N.ptr(ws.xa), N.ptr(ws.ua), N.ptr(K), N.ptr(k), bounds,
+                   N.ptr(zI), float(linesearch_decay), int(max_linesearch_iter), N.ptr(ws.xb), N.ptr(ws.ub),
+                   N.ptr(ws.cost), N.ptr(ws.du_sq), N.ptr(ws.alpha), prev, s)
         N.call("dilqr_mpc_update_best_f32", n, m, T, B, int(i == 0), float(best_cost_eps), float(eps),
                int(min(not_improved_lim, 2 ** 31 - 1)), N.ptr(ws.xb), N.ptr(ws.ub), N.ptr(ws.cost),
                N.ptr(ws.du_sq), N.ptr(ws.fdn), N.ptr(ws.best_x), N.ptr(ws.best_u), N.ptr(ws.best_cost),

@@ -50,6 +50,12 @@ extern "C" {
                                     implicit backward, get_matrices, grad_input
                                     and the dynamics VJP return DILQR_E_SHAPE */
 
+#define DILQR_MODEL_MLP 5        /* dynamics.py:15-130 NNDynamics with one hidden
+                                    layer; described by a dilqr_mlp, served by
+                                    the dilqr_mlp_* entry points below (the
+                                    entry points that take `model` and theta
+                                    return DILQR_E_SHAPE for it)                  */
+
 /* ---- control bounds (MPC u_lower/u_upper: float or [T,B,m] tensor) -------- */
 #define DILQR_BOUNDS_NONE 0
 #define DILQR_BOUNDS_SCALAR 1    /* lo/hi are floats                              */
@@ -67,7 +73,7 @@ typedef struct dilqr_bounds {
   const float* hi_t;             /* [T,B,m] or NULL                              */
 } dilqr_bounds;
 
-/* Library version (for the loader's sanity check): 8. */
+/* Library version (for the loader's sanity check): 10. */
 int dilqr_version(void);
 
 /* Build id: the first 16 hex digits of the sha256 of the sources the library
@@ -400,6 +406,66 @@ int dilqr_mpc_solve_small_f32(int model, int T, int B, const float* theta, const
 /* Materialise each problem's best trajectory into x_out [T,B,n], u_out [T,B,m]. */
 int dilqr_mpc_gather_best_f32(int n, int m, int T, int B, dilqr_mpc_state st, float* x_out,
                               float* u_out, void* stream);
+
+/* ---- learned dynamics: a one-hidden-layer network (ABI 10) ----------------- */
+/* The reference's NNDynamics (dynamics.py:15-130) with len(hidden_sizes) == 1:
+     x' = W2 act(W1 [x;u] + b1) + b2   (+ x with passthrough),
+   act = sigmoid or relu (the two its grad_input covers, dynamics.py:107-118).
+   The weights are torch's own nn.Linear storage, read in place: W1 [H, n+m],
+   b1 [H], W2 [n, H], b2 [n], fp32 contiguous device buffers, 16-byte aligned.
+   1 <= H = n_hidden <= DILQR_MLP_MAX_HIDDEN; (n, m) one of the one-lane-per-
+   problem shapes of the Riccati sweep ((3,1) (5,1) (4,3) (4,1) (2,1) (4,2)
+   (6,2) (6,1)).  One row (problem) per lane; every lane reads the weights at
+   the same address.  No control clamp (the network has none).
+   Errors, all before any launch: DILQR_E_ARG for a null or misaligned pointer
+   or a bad size, DILQR_E_SHAPE for an unsupported (n, m) or H outside
+   [1, DILQR_MLP_MAX_HIDDEN], DILQR_E_MODE for an unknown activation. */
+#define DILQR_MLP_SIGMOID 0
+#define DILQR_MLP_RELU 1
+#define DILQR_MLP_MAX_HIDDEN 256
+
+typedef struct dilqr_mlp {
+  int n_hidden;                  /* H                                             */
+  int activation;                /* DILQR_MLP_*                                   */
+  int passthrough;               /* != 0: x' += x, and I on the Jacobian's state block */
+  const float* W1;               /* [H, n+m]  fcs[0].weight                       */
+  const float* b1;               /* [H]       fcs[0].bias                         */
+  const float* W2;               /* [n, H]    fcs[1].weight                       */
+  const float* b2;               /* [n]       fcs[1].bias                         */
+} dilqr_mlp;
+
+/* x' for N independent rows: NNDynamics.forward, dynamics.py:66-90.
+   x [N,n], u [N,m], out [N,n]. */
+int dilqr_mlp_dynamics_f32(int n, int m, int N, dilqr_mlp mlp, const float* x,
+                           const float* u, float* out, void* stream);
+
+/* D = [R S] = d x' / d [x;u], [N,n,n+m]: NNDynamics.grad_input,
+   dynamics.py:92-130 (W2 diag(act') W1, + I on the state block with
+   passthrough; act' = a(1-a) for sigmoid, (a > 0) for relu). */
+int dilqr_mlp_linear_dyn_f32(int n, int m, int N, dilqr_mlp mlp, const float* x,
+                             const float* u, float* D, void* stream);
+
+/* Rollout x_{t+1} = mlp(x_t, u_t) from x_init: util.get_traj, util.py:104-127. */
+int dilqr_mlp_rollout_f32(int n, int m, int T, int B, dilqr_mlp mlp, const float* x_init,
+                          const float* u, float* x_out, void* stream);
+
+/* Linearisation around (x,u): F = [R S](x_t,u_t), f = mlp(x_t,u_t) - R x_t - S u_t,
+   t < T-1: MPC.linearize_dynamics ANALYTIC with grad_input, mpc.py:494-519.
+   One walk over the hidden units gives the value and the Jacobian of a row. */
+int dilqr_mlp_linearize_f32(int n, int m, int T, int B, dilqr_mlp mlp, const float* x,
+                            const float* u, float* F, float* f, void* stream);
+
+/* dilqr_lqr_forward_f32 with the network as the true dynamics: the rollout
+   with per-problem backtracking line search, lqr_forward,
+   lqr_step_explicit.py:166-263 (226-236: true_dynamics a Module).  Bounds,
+   u_zero_I, outputs and old_cost as there. */
+int dilqr_mlp_lqr_forward_f32(int n, int m, int T, int B, dilqr_mlp mlp, const float* x_init,
+                              const float* C, const float* c, const float* x,
+                              const float* u, const float* K, const float* k,
+                              dilqr_bounds bounds, const unsigned char* u_zero_I,
+                              float linesearch_decay, int max_linesearch_iter,
+                              float* x_out, float* u_out, float* cost, float* du_sq,
+                              float* alpha, const float* old_cost, void* stream);
 
 #ifdef __cplusplus
 }

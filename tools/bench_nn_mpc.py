@@ -1,0 +1,162 @@
+#!/usr/bin/env python
+"""Time an MPC solve with learned dynamics (NNDynamics) on the GPU, device MLP
+kernels against the torch loop, on the same inputs in one process.
+
+Workload: NNDynamics(5, 1, [100], sigmoid), T = 25, lqr_iter = 10 fixed-count
+(eps = 0, not_improved_lim huge), controls in [-1, 1], a dense SPD cost, one
+whole mpc.MPC.forward under no_grad.  Batches 32, 4096, 65536.  The arm with
+generic.DEVICE_MLP = False is the torch loop (the path before the MLP kernels
+existed).  Per batch and arm: warm-up solves, then repeated solves timed with
+device events, the two arms alternating; median, min and max are printed, and
+the costs of the two arms are compared.  Then the linearisation kernel alone
+at the largest batch, with its bytes and FLOPs per row.
+
+    python tools/bench_nn_mpc.py [--batches 32,4096,65536] [--out FILE]
+"""
+import argparse
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "differentiable-ilqr_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+N_STATE, N_CTRL, HIDDEN, T, LQR_ITER = 5, 1, 100, 25, 10
+PEAK_FP32_FMA = 157.3e12 / 2      # v_fma_f32, unpacked: half the packed-FMA vector peak
+PEAK_HBM = 6.29e12                # measured float4 copy
+
+
+def commit():
+    try:
+        out = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True)
+        dirty = subprocess.run(["git", "-C", ROOT, "status", "--porcelain"], capture_output=True, text=True)
+        if out.returncode == 0:
+            return out.stdout.strip() + ("+changes" if dirty.stdout.strip() else "")
+    except OSError:
+        pass
+    return os.environ.get("DILQR_COMMIT", "unknown")
+
+
+def problem(B, dev):
+    g = torch.Generator().manual_seed(1234)
+    d = N_STATE + N_CTRL
+    L = torch.randn(T, B, d, d, generator=g)
+    C = L @ L.transpose(-1, -2) + 0.5 * torch.eye(d)
+    c = torch.randn(T, B, d, generator=g)
+    x0 = torch.randn(B, N_STATE, generator=g)
+    return x0.to(dev), C.to(dev), c.to(dev)
+
+
+def solver(B):
+    import dilqr.mpc as cmpc
+    return cmpc.MPC(N_STATE, N_CTRL, T, lqr_iter=LQR_ITER, grad_method=cmpc.GradMethods.ANALYTIC, u_lower=-1.0,
+                    u_upper=1.0, n_batch=B, eps=0.0, not_improved_lim=10 ** 9, exit_unconverged=False,
+                    detach_unconverged=False, linesearch_decay=0.2, max_linesearch_iter=10, verbose=-1)
+
+
+def timed_solve(mpc, x0, cost, dx):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    with torch.no_grad():
+        x, u, costs = mpc(x0, cost, dx)
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b), costs
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="32,4096,65536")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--budget", type=float, default=60.0, help="seconds of timed solves per batch and arm")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_nn_mpc: needs a GPU (no CPU timing)")
+    from dilqr import QuadCost, generic, ops
+    from dilqr.dynamics import NNDynamics
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    dx = NNDynamics(N_STATE, N_CTRL, hidden_sizes=[HIDDEN], activation="sigmoid").to(dev)
+    lines = [f"# bench_nn_mpc  commit {commit()}  lib {os.environ.get('DILQR_LIB', 'dilqr/libdilqr.so')}",
+             f"# NNDynamics({N_STATE},{N_CTRL},[{HIDDEN}],sigmoid) T={T} lqr_iter={LQR_ITER} fixed-count, u in [-1,1], "
+             f"dense SPD cost; one mpc.MPC.forward under no_grad; device events; ms",
+             f"# {torch.cuda.get_device_name(0)}  torch {torch.__version__}",
+             "B        arm     n   median_ms      min_ms      max_ms   speedup   max_rel_cost_diff"]
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    for s in lines:
+        print(s, flush=True)
+    for B in [int(b) for b in args.batches.split(",")]:
+        x0, C, c = problem(B, dev)
+        cost, mpc = QuadCost(C, c), solver(B)
+        times, costs = {True: [], False: []}, {}
+        for flag in (True, False):
+            generic.DEVICE_MLP = flag
+            for _ in range(args.warmup if flag else 1):
+                timed_solve(mpc, x0, cost, dx)
+        spent = {True: 0.0, False: 0.0}
+        for r in range(args.repeats):                      # the arms alternate
+            for flag in (True, False):
+                if r >= 3 and spent[flag] > args.budget:
+                    continue
+                generic.DEVICE_MLP = flag
+                t0 = time.perf_counter()
+                ms, cs = timed_solve(mpc, x0, cost, dx)
+                spent[flag] += time.perf_counter() - t0
+                times[flag].append(ms)
+                costs[flag] = cs
+        generic.DEVICE_MLP = True
+        rel = float(((costs[True] - costs[False]).abs() / costs[False].abs().clamp(min=1.0)).max())
+        med = {f: statistics.median(times[f]) for f in times}
+        for flag, name in ((False, "torch"), (True, "device")):
+            t = times[flag]
+            emit(f"{B:<8d} {name:<7s} {len(t):<3d} {med[flag]:11.3f} {min(t):11.3f} {max(t):11.3f} "
+                 f"{med[False] / med[flag]:9.2f}   {rel:.2e}")
+        del x0, C, c, cost
+        torch.cuda.empty_cache()
+    # the linearisation kernel alone at the largest batch
+    B = max(int(b) for b in args.batches.split(","))
+    md = dx.device_model(torch.zeros(1, device=dev))
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(T, B, N_STATE, generator=g).to(dev)
+    u = torch.randn(T, B, N_CTRL, generator=g).clamp(-1, 1).to(dev)
+    for _ in range(3):
+        ops.mlp_linearize(md, x, u)
+    ts = []
+    for _ in range(20):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        ops.mlp_linearize(md, x, u)
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    n, m, d, H = N_STATE, N_CTRL, N_STATE + N_CTRL, HIDDEN
+    rows = (T - 1) * B
+    byts, flops = (d + n * d + n) * 4, 2 * H * (d + 2 * n + n * d)
+    t = statistics.median(ts) * 1e-3
+    emit(f"# mlp_linearize B={B}: {rows} rows, call (allocation + kernel, device events) median "
+         f"{t * 1e3:.3f} ms, min {min(ts):.3f}, max {max(ts):.3f}")
+    emit(f"#   per row {byts} B, {flops} FLOP: {rows * byts / t / 1e12:.3f} TB/s "
+         f"({100 * rows * byts / t / PEAK_HBM:.1f}% of {PEAK_HBM / 1e12:.2f} TB/s measured copy), "
+         f"{rows * flops / t / 1e12:.2f} TFLOP/s ({100 * rows * flops / t / PEAK_FP32_FMA:.1f}% of "
+         f"{PEAK_FP32_FMA / 1e12:.1f} TFLOP/s unpacked fp32 FMA)")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
