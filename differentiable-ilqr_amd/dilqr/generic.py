@@ -16,6 +16,11 @@ One Module is not run by torch: an NNDynamics with a device model (one hidden
 layer, sigmoid or relu; NNDynamics.device_model) goes through the HIP MLP
 kernels — see DEVICE_MLP below.
 
+lqr_step_forward is the one regular forward of an LQR step: the LQRStep
+factories (lqr_step.py, lqr_step_explicit.py) call it too.  Whether its line
+search runs in the kernels (on an ops.Dynamics handle) or in torch is decided
+in one place, line_search_dynamics.
+
 Nothing here is on the HIP hot path of the headline: those solves go through
 ops.mpc_solve.  This module exists so that a user of the reference with any
 dynamics or cost finds the same MPC API working on the GPU.
@@ -64,10 +69,8 @@ DEVICE_MLP = True
 
 def device_mlp(dynamics, like):
     """dynamics' ops.MlpModel for tensors like `like` (a GPU fp32 tensor), or None."""
-    if not DEVICE_MLP or isinstance(dynamics, LinDx) or not like.is_cuda or like.dtype != torch.float32:
-        return None
-    make = getattr(dynamics, "device_model", None)
-    return None if make is None else make(like)
+    dyn = ops.device_dynamics(dynamics, like, env=False, mlp=DEVICE_MLP)
+    return None if dyn is None else dyn.mlp
 
 
 def device_solve_ok(mpc, cost, dx, x_init):
@@ -112,6 +115,14 @@ class SlewRateCost(torch.nn.Module):
         return self.cost(tau[:, self.n_ctrl:]) + 0.5 * bquad(tau, self.slew_C[0])
 
 
+def next_state(dynamics, t, x, u):
+    """x_{t+1}: a LinDx's F_t [x; u] (+ f_t), any other dynamics called as a Module."""
+    if not isinstance(dynamics, LinDx):
+        return dynamics(x, u)
+    nx = bmv(dynamics.F[t], torch.cat((x, u), 1))
+    return nx if dynamics.f is None or dynamics.f.nelement() == 0 else nx + dynamics.f[t]
+
+
 def rollout(T, u, x_init, dynamics):
     """util.get_traj (util.py:104-127)."""
     mlp = device_mlp(dynamics, x_init)
@@ -120,13 +131,7 @@ def rollout(T, u, x_init, dynamics):
     x = [x_init.detach()]
     with torch.no_grad():
         for t in range(T - 1):
-            if isinstance(dynamics, LinDx):
-                nx = bmv(dynamics.F[t], torch.cat((x[t], u[t]), 1))
-                if dynamics.f is not None and dynamics.f.nelement() > 0:
-                    nx = nx + dynamics.f[t]
-            else:
-                nx = dynamics(x[t], u[t].detach())
-            x.append(nx.detach())
+            x.append(next_state(dynamics, t, x[t], u[t].detach()).detach())
     return torch.stack(x, 0)
 
 
@@ -252,46 +257,61 @@ def approximate_cost(x, u, cost, diff):
 
 
 # ---------------------------------------------------------------- one LQR step (forward)
+def line_search_dynamics(true_cost, true_dynamics, x, delta_u, env_models):
+    """The ops.Dynamics handle the step's line search runs on in the kernels, or
+    None for the torch loop.  This is the whole routing rule of an LQR step:
+      * not a QuadCost -> torch;
+      * an env_dx model or a LinDx (env_models: asked for by the LQRStep
+        factories only; the generic MPC loop has always run them in torch, its
+        own use of them being delta_u, the slew-rate penalty and the autograd /
+        finite-difference linearisations) -> device, with any delta_u;
+      * a dynamics Module with a device model (DEVICE_MLP) -> device only without
+        delta_u and with the full [T,B,d,d] / [T,B,d] QuadCost.  delta_u is left
+        out because that combination was not built or tested on the MLP entry
+        point, not because the kernel cannot clamp to per-step tensor bounds;
+      * any other Module -> torch."""
+    if not isinstance(true_cost, QuadCost):
+        return None
+    dyn = ops.device_dynamics(true_dynamics, x, env=env_models, mlp=DEVICE_MLP)
+    if dyn is None or dyn.mlp is None:
+        return dyn
+    T, B, d = x.shape[0], x.shape[1], dyn.n + dyn.m
+    full = tuple(true_cost.C.shape) == (T, B, d, d) and tuple(true_cost.c.shape) == (T, B, d)
+    return dyn if delta_u is None and full else None
+
+
 def lqr_step_forward(T, n, m, x_init, C, c, F, x, u, true_cost, true_dynamics, u_lower, u_upper, delta_u,
-                     decay, max_ls, u_zero_I=None, extras=False):
-    """LQRStepFn.forward of the DiLQR step (lqr_step_explicit.py:625-650): the
-    HIP Riccati sweep in delta space (c_back = C tau + c fused), then the line
-    search of lqr_forward (166-263) with the true dynamics/cost.  Returns
-    (new_x, new_u, costs [B], full_du_norm [B]); with extras also the final
-    step sizes [B] (one decay undone where the last pass still failed,
-    254-255) and the sweep's pnqp iteration count."""
+                     decay, max_ls, u_zero_I=None, extras=False, env_models=False):
+    """LQRStepFn.forward of the DiLQR step (lqr_step_explicit.py:625-650), the
+    one regular forward of both LQRStep factories and of the generic loop: the
+    HIP Riccati sweep in delta space (ops.delta_sweep), then the line search of
+    lqr_forward (166-263) with the true dynamics/cost, in the kernels or in
+    torch as line_search_dynamics rules.  Returns (new_x, new_u, costs [B],
+    full_du_norm [B]); with extras also the final step sizes [B] (in torch one
+    decay undone where the last pass still failed, 254-255) and the sweep's
+    pnqp iteration count (formed only then, and only with bounds)."""
     B = x.shape[1]
-    lo = u_lower if (u_lower is None or isinstance(u_lower, float)) else u_lower.detach().contiguous()
-    hi = u_upper if (u_upper is None or isinstance(u_upper, float)) else u_upper.detach().contiguous()
+    lo, hi = (v if v is None or isinstance(v, (int, float)) else v.detach().contiguous() for v in (u_lower, u_upper))
     if delta_u is not None and lo is None:
         raise NotImplementedError("dilqr: delta_u without u_lower is unimplemented in the reference too "
                                   "(lqr_step_explicit.py:197)")
-    zI = None if u_zero_I is None else u_zero_I.detach().bool()
+    zI = None if u_zero_I is None else u_zero_I.detach()
     xd, ud = x.detach().contiguous(), u.detach().contiguous()
-    Cd, cd, Fd = C.detach().contiguous(), c.detach().contiguous(), F.detach().contiguous()
-    if delta_u is not None:
-        # lqr_step_explicit.py:132-135: the sweep's relative box clipped to
-        # +-delta_u (exact values), c_back formed here
-        rlo, rhi = ops.delta_u_sweep_bounds(lo, hi, ud, delta_u)
-        K, k, nqp = ops.lqr_backward(Cd, ops.c_back(Cd, cd, xd, ud), Fd, n, m, u_lower=rlo, u_upper=rhi,
-                                     qp_total=extras)
-    else:
-        K, k, nqp = ops.lqr_backward(Cd, cd, Fd, n, m, x=xd, u=ud, u_lower=lo, u_upper=hi,
-                                     u_zero_I=zI if lo is None else None, qp_total=extras and lo is not None)
-    mlp = None
-    if isinstance(true_cost, QuadCost) and delta_u is None and tuple(true_cost.C.shape) == (T, B, n + m, n + m) \
-            and tuple(true_cost.c.shape) == (T, B, n + m):
-        mlp = device_mlp(true_dynamics, x)
-    if mlp is not None:
-        # the line search on device (k_lqr_forward on the MLP model): the same
-        # per-problem rule; du_sq is the first pass's, alphas the last pass's
+    K, k, nqp = ops.delta_sweep(C.detach().contiguous(), c.detach().contiguous(), F.detach().contiguous(), n, m,
+                                xd, ud, lo, hi, zI, delta_u, qp_total=extras and lo is not None)
+    n_qp = nqp if isinstance(nqp, int) else 0
+    # with delta_u the rollout's clamp is u_t +- delta_u cut to the bounds (205-213)
+    flo, fhi = (lo, hi) if delta_u is None else ops.delta_u_rollout_bounds(lo, hi, ud, delta_u)
+    dyn = line_search_dynamics(true_cost, true_dynamics, xd, delta_u, env_models)
+    if dyn is not None:
+        # the same per-problem rule on device; du_sq is the first pass's, alphas the last pass's
         new_x, new_u, cur_cost, du_sq, alphas = ops.lqr_forward(
-            mlp, None, x_init.detach(), true_cost.C.detach(), true_cost.c.detach(), xd, ud, K, k, u_lower=lo,
-            u_upper=hi, u_zero_I=zI, linesearch_decay=decay, max_linesearch_iter=max_ls)
+            dyn, None, x_init.detach(), true_cost.C.detach(), true_cost.c.detach(), xd, ud, K, k, u_lower=flo,
+            u_upper=fhi, u_zero_I=zI, linesearch_decay=decay, max_linesearch_iter=max_ls)
         full_du_norm = ops.quirk_norm(du_sq)
-        if extras:
-            return new_x, new_u, cur_cost, full_du_norm, alphas, (nqp if isinstance(nqp, int) else 0)
-        return new_x, new_u, cur_cost, full_du_norm
+        return (new_x, new_u, cur_cost, full_du_norm) + ((alphas, n_qp) if extras else ())
+    if zI is not None:
+        zI = zI.bool()
     old_cost = traj_cost(T, x, u, true_cost)
     alphas = torch.ones(B, device=x.device)
     cur_cost, full_du_norm = None, None
@@ -303,25 +323,12 @@ def lqr_step_forward(T, n, m, x_init, C, c, F, x, u, true_cost, true_dynamics, u
                 nu = bmv(K[t], dxs) + u[t] + alphas.unsqueeze(1) * k[t]
                 if zI is not None:                              # lqr_step_explicit.py:199-200
                     nu = torch.where(zI[t], torch.zeros_like(nu), nu)
-                if lo is not None:
-                    lb = lo if isinstance(lo, float) else lo[t]
-                    ub = hi if isinstance(hi, float) else hi[t]
-                    if delta_u is not None:                 # lqr_step_explicit.py:205-213
-                        lb_lim, ub_lim = lb, ub
-                        lb = u[t] - delta_u
-                        ub = u[t] + delta_u
-                        lb = torch.where(lb < lb_lim, torch.as_tensor(lb_lim, device=lb.device).expand_as(lb), lb)
-                        ub = torch.where(ub > ub_lim, torch.as_tensor(ub_lim, device=ub.device).expand_as(ub), ub)
-                    nu = eclamp(nu, lb, ub)
+                if flo is not None:
+                    nu = eclamp(nu, *(v if isinstance(v, (int, float)) else v[t] for v in (flo, fhi)))
                 new_u.append(nu)
                 tau = torch.cat((new_x[t], nu), 1)
                 if t < T - 1:
-                    if isinstance(true_dynamics, LinDx):
-                        nx = bmv(true_dynamics.F[t], tau)
-                        if true_dynamics.f is not None and true_dynamics.f.nelement() > 0:
-                            nx = nx + true_dynamics.f[t]
-                    else:
-                        nx = true_dynamics(new_x[t], nu)
+                    nx = next_state(true_dynamics, t, new_x[t], nu)
                     new_x.append(nx)
                     dxs = nx - x[t + 1]
                 if isinstance(true_cost, QuadCost):
@@ -337,10 +344,7 @@ def lqr_step_forward(T, n, m, x_init, C, c, F, x, u, true_cost, true_dynamics, u
             i += 1
         if extras:
             alphas = torch.where(cur_cost > old_cost, alphas / decay, alphas)
-    if extras:
-        n_qp = nqp if isinstance(nqp, int) else 0
-        return new_x, new_u, cur_cost, full_du_norm, alphas, n_qp
-    return new_x, new_u, cur_cost, full_du_norm
+    return (new_x, new_u, cur_cost, full_du_norm) + ((alphas, n_qp) if extras else ())
 
 
 # ---------------------------------------------------------------- the slew-rate augmentation
@@ -410,20 +414,18 @@ def solve(mpc, x_init, cost, dx, n_batch):
         # the whole loop on device: rollout, linearise, sweep, line search and the
         # best-iterate / stop rule, four launches per iteration, no host poll
         # between them (ops.mpc_solve_unfused on the MLP model)
+        from .mpc_explicit import MPC
         with torch.no_grad():
             ws = ops.mpc_solve_unfused(
                 mlp, None, x_init.detach(), cost.C.detach().contiguous(), cost.c.detach().contiguous(), T,
-                u_init=mpc.u_init, u_lower=mpc.u_lower, u_upper=mpc.u_upper, lqr_iter=mpc.lqr_iter, eps=mpc.eps,
-                linesearch_decay=mpc.linesearch_decay, max_linesearch_iter=mpc.max_linesearch_iter,
-                not_improved_lim=mpc.not_improved_lim, best_cost_eps=mpc.best_cost_eps,
-                u_zero_I=getattr(mpc, "u_zero_I", None))
+                u_zero_I=getattr(mpc, "u_zero_I", None), **MPC.solver_args(mpc))
         return ws.best_x, ws.best_u, ws.best_cost, ws.best_du
     if mpc.u_init is None:
         u = torch.zeros(T, n_batch, m, device=dev, dtype=x_init.dtype)
     else:
-        u = mpc.u_init.to(device=dev, dtype=x_init.dtype)
-        if u.ndimension() == 2:
-            u = u.unsqueeze(1).expand(T, n_batch, -1).clone()
+        u = ops.expand_u_init(mpc.u_init, T, n_batch, -1, dev, x_init.dtype)
+        if mpc.u_init.ndimension() == 2:
+            u = u.clone()
     x_init = x_init.detach()
     best = None
     n_not_improved = 0

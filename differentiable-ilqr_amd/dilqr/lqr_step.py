@@ -10,7 +10,6 @@ from torch.autograd import Function
 
 from . import _native as N
 from . import generic, ops
-from .definitions import QuadCost
 
 
 def LQRStep(n_state, n_ctrl, T, u_lower=None, u_upper=None, u_zero_I=None, delta_u=None,
@@ -32,35 +31,11 @@ def LQRStep(n_state, n_ctrl, T, u_lower=None, u_upper=None, u_zero_I=None, delta
             if no_op_forward:                                   # lqr_step.py:277-282
                 ctx.save_for_backward(x_init, C, c, F, f, x, u)
                 return x.clone(), u.clone()
-            m_id = ops.generic_model_id(true_dynamics)
-            if not isinstance(true_cost, QuadCost) or m_id is None:
-                # a generic true_cost / true_dynamics (lqr_step.py:224-234): the HIP
-                # sweep, the rollout with the user's Modules in torch
-                nx, nu, costs, full_du_norm, alphas, n_qp = generic.lqr_step_forward(
-                    T, n_state, n_ctrl, x_init, C, c, F, x, u, true_cost, true_dynamics, lo, hi, delta_u,
-                    linesearch_decay, max_linesearch_iter, u_zero_I=zI, extras=True)
-                ctx.save_for_backward(x_init, C, c, F, f, nx, nu)
-                return nx, nu, torch.tensor([float(n_qp)]), costs, full_du_norm, alphas.mean()
-            if delta_u is not None:                             # lqr_step.py:130-135
-                rlo, rhi = ops.delta_u_sweep_bounds(lo, hi, u, delta_u)
-                K, k, nqp = ops.lqr_backward(C, ops.c_back(C.detach(), c.detach(), x, u), F, n_state, n_ctrl,
-                                             u_lower=rlo, u_upper=rhi, qp_total=True)
-            else:
-                K, k, nqp = ops.lqr_backward(C, c, F, n_state, n_ctrl, x=x, u=u, u_lower=lo, u_upper=hi,
-                                             u_zero_I=zI if lo is None else None, qp_total=lo is not None)
-            if m_id == N.MODEL_LINDX:
-                th, Fd, fd = None, true_dynamics.F, true_dynamics.f
-                if fd is not None and fd.nelement() == 0:
-                    fd = None
-            else:
-                th, Fd, fd = ops.theta_of(true_dynamics, x_init), None, None
-            Ct, ct = true_cost
-            flo, fhi = (lo, hi) if delta_u is None else ops.delta_u_rollout_bounds(lo, hi, u, delta_u)
-            nx, nu, costs, du_sq, alphas = ops.lqr_forward(
-                m_id, th, x_init, Ct, ct, x, u, K, k, F=Fd, f=fd, u_lower=flo, u_upper=fhi, u_zero_I=zI,
-                linesearch_decay=linesearch_decay, max_linesearch_iter=max_linesearch_iter)
-            full_du_norm = ops.quirk_norm(du_sq)
-            n_qp = nqp if isinstance(nqp, int) else 0
+            # lqr_step.py:130-135, 224-234: the shared step (sweep, then the line
+            # search on device or with the user's Modules in torch)
+            nx, nu, costs, full_du_norm, alphas, n_qp = generic.lqr_step_forward(
+                T, n_state, n_ctrl, x_init, C, c, F, x, u, true_cost, true_dynamics, lo, hi, delta_u,
+                linesearch_decay, max_linesearch_iter, u_zero_I=zI, extras=True, env_models=True)
             ctx.save_for_backward(x_init, C, c, F, f, nx, nu)
             return nx, nu, torch.tensor([float(n_qp)]), costs, full_du_norm, alphas.mean()
 

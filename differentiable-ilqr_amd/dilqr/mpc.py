@@ -11,8 +11,6 @@ F comes from the kernel and, when dx.params requires grad, f is formed the same
 way through the model's device vjp, so gradients reach (x_init, C, c), the
 parameters and, for LinDx, (F, f).
 """
-import warnings
-
 import torch
 from torch.nn import Module
 
@@ -64,6 +62,7 @@ class MPC(Module):
     # generic dynamics / costs share the explicit MPC's driver
     forward_generic = ExplicitMPC.forward_generic
     _detach_unconverged = ExplicitMPC._detach_unconverged
+    solver_args = ExplicitMPC.solver_args
 
     def fused(self, cost, dx):
         """The device-resident loop: env_dx model (ANALYTIC) or LinDx, quadratic
@@ -101,32 +100,19 @@ class MPC(Module):
             raise ValueError("MPC Error: Could not infer batch size, pass in as n_batch")
         T, n, m = self.T, self.n_state, self.n_ctrl
         C, c = expand_cost(cost.C, cost.c, T, n_batch, n + m)
-        model_id = ops.model_id_of(dx)
+        dyn = ops.device_dynamics(dx, x_init)
+        model_id = dyn.model_id
         lin = model_id == N.MODEL_LINDX
-        theta = None if lin else ops.theta_of(dx, x_init)
-        Fd = fd = None
-        if lin:
-            Fd = dx.F.detach().contiguous()
-            fd = None if (dx.f is None or dx.f.nelement() == 0) else dx.f.detach().contiguous()
         with torch.no_grad():
             if not lin and self.u_zero_I is None:
                 # an env_dx model: the device-resident fused loop (its iterates equal
                 # the unfused pipeline's bit for bit, test_fused_iteration_equals_unfused)
                 x, u, costs, full_du_norm, _sv = ops.mpc_solve(
-                    model_id, theta, x_init.detach(), C.detach().contiguous(), c.detach().contiguous(), T,
-                    u_init=self.u_init, u_lower=self.u_lower, u_upper=self.u_upper, lqr_iter=self.lqr_iter,
-                    eps=self.eps, linesearch_decay=self.linesearch_decay,
-                    max_linesearch_iter=self.max_linesearch_iter, not_improved_lim=self.not_improved_lim,
-                    best_cost_eps=self.best_cost_eps, verbose=self.verbose)
+                    model_id, dyn.theta, x_init.detach(), C.detach().contiguous(), c.detach().contiguous(), T,
+                    **self.solver_args())
             else:
-                ws = ops.mpc_solve_unfused(model_id, theta, x_init.detach(), C.detach().contiguous(),
-                                           c.detach().contiguous(), T, F=Fd, f=fd, u_init=self.u_init,
-                                           u_lower=self.u_lower, u_upper=self.u_upper, lqr_iter=self.lqr_iter,
-                                           eps=self.eps, linesearch_decay=self.linesearch_decay,
-                                           max_linesearch_iter=self.max_linesearch_iter,
-                                           not_improved_lim=self.not_improved_lim,
-                                           best_cost_eps=self.best_cost_eps, u_zero_I=self.u_zero_I,
-                    verbose=self.verbose)
+                ws = ops.mpc_solve_unfused(dyn, None, x_init.detach(), C.detach().contiguous(),
+                                           c.detach().contiguous(), T, u_zero_I=self.u_zero_I, **self.solver_args())
                 x, u, costs, full_du_norm, _sv = ws.best_x, ws.best_u, ws.best_cost, ws.best_du, ws
         if self.verbose > 0:                                    # mpc.py:270-275, 368-379
             from .util import print_solve_log
@@ -135,7 +121,7 @@ class MPC(Module):
             if lin:
                 F, f = dx.F, (dx.f if dx.f is not None else torch.empty(0, device=x.device))
             else:
-                F, f = ops.linearize(model_id, theta, x, u)
+                F, f = ops.linearize(dyn, None, x, u)
                 params = getattr(dx, "params", None)
                 if isinstance(params, torch.Tensor) and params.requires_grad:
                     f = self._f_with_params_graph(dx, model_id, F, x, u)
@@ -143,15 +129,4 @@ class MPC(Module):
                            true_cost=QuadCost(C, c), true_dynamics=dx, current_x=x, current_u=u,
                            back_eps=self.back_eps, no_op_forward=True)
             x, u = step(x_init, C, c, F, f)
-        if self.detach_unconverged and float(full_du_norm.max()) > self.eps:    # mpc.py:321-334
-            if self.exit_unconverged:
-                raise AssertionError("LQR did not converge (exit_unconverged=True)")
-            if self.verbose >= 0:
-                warnings.warn("LQR Warning: All examples did not converge to a fixed point. "
-                              "Detaching and *not* backpropping through the bad examples.")
-            I = (full_du_norm < self.eps)
-            Ix = I.view(1, -1, 1).expand_as(x).to(x.dtype)
-            Iu = I.view(1, -1, 1).expand_as(u).to(u.dtype)
-            x = x * Ix + x.clone().detach() * (1. - Ix)
-            u = u * Iu + u.clone().detach() * (1. - Iu)
-        return x, u, costs
+        return self._detach_unconverged(x, u, costs, full_du_norm)            # mpc.py:321-334

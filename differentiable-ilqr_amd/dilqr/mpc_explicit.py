@@ -13,9 +13,8 @@ from enum import Enum
 import torch
 from torch.nn import Module
 
-from . import _native as N
 from . import ops
-from .definitions import LinDx, QuadCost
+from .definitions import QuadCost
 from .lqr_step_explicit import LQRStep
 
 
@@ -86,6 +85,14 @@ class MPC(Module):
         return (isinstance(cost, QuadCost) and getattr(dx, "model_id", None) is not None and jac_ok
                 and self.slew_rate_penalty is None and self.delta_u is None)
 
+    def solver_args(self):
+        """The constructor's options as the keywords ops.mpc_solve and
+        ops.mpc_solve_unfused take them."""
+        return dict(u_init=self.u_init, u_lower=self.u_lower, u_upper=self.u_upper, lqr_iter=self.lqr_iter,
+                    eps=self.eps, linesearch_decay=self.linesearch_decay,
+                    max_linesearch_iter=self.max_linesearch_iter, not_improved_lim=self.not_improved_lim,
+                    best_cost_eps=self.best_cost_eps, verbose=self.verbose)
+
     def forward(self, x_init, cost, dx):
         if not x_init.is_cuda:
             raise RuntimeError("dilqr: x_init must be on the GPU (no CPU path)")
@@ -98,26 +105,17 @@ class MPC(Module):
         T, n, m = self.T, self.n_state, self.n_ctrl
         C, c = expand_cost(cost.C, cost.c, T, n_batch, n + m)
         assert x_init.ndimension() == 2 and x_init.size(0) == n_batch
-        model_id = ops.model_id_of(dx)
-        theta = ops.theta_of(dx, x_init)
+        dyn = ops.device_dynamics(dx, x_init)
         Cd, cd = C.detach().contiguous(), c.detach().contiguous()
         with torch.no_grad():
             if self.u_zero_I is None:
-                x, u, costs, full_du_norm, sv = ops.mpc_solve(
-                    model_id, theta, x_init.detach(), Cd, cd, T, u_init=self.u_init, u_lower=self.u_lower,
-                    u_upper=self.u_upper, lqr_iter=self.lqr_iter, eps=self.eps,
-                    linesearch_decay=self.linesearch_decay, max_linesearch_iter=self.max_linesearch_iter,
-                    not_improved_lim=self.not_improved_lim, best_cost_eps=self.best_cost_eps,
-                    verbose=self.verbose)
+                x, u, costs, full_du_norm, sv = ops.mpc_solve(dyn.model_id, dyn.theta, x_init.detach(), Cd, cd, T,
+                                                              **self.solver_args())
             else:
                 # controls held at zero (mpc_explicit.py:369, 452 -> LQRStep u_zero_I):
                 # the unfused kernels take the mask (masked gain solve, zeroed rollout)
-                sv = ops.mpc_solve_unfused(
-                    model_id, theta, x_init.detach(), Cd, cd, T, u_init=self.u_init, u_lower=self.u_lower,
-                    u_upper=self.u_upper, lqr_iter=self.lqr_iter, eps=self.eps,
-                    linesearch_decay=self.linesearch_decay, max_linesearch_iter=self.max_linesearch_iter,
-                    not_improved_lim=self.not_improved_lim, best_cost_eps=self.best_cost_eps, u_zero_I=self.u_zero_I,
-                    verbose=self.verbose)
+                sv = ops.mpc_solve_unfused(dyn, None, x_init.detach(), Cd, cd, T, u_zero_I=self.u_zero_I,
+                                           **self.solver_args())
                 x, u, costs, full_du_norm = sv.best_x, sv.best_u, sv.best_cost, sv.best_du
         self.last_solve = sv
         if self.verbose > 0:
@@ -130,7 +128,7 @@ class MPC(Module):
         if need_grad:
             # mpc_explicit.py:302-325: linearise at the best iterate and hand theta
             # to the implicit backward through a no-op LQR step.
-            F, f = ops.linearize(model_id, theta, x, u)
+            F, f = ops.linearize(dyn, None, x, u)
             th = dx.params if isinstance(dx.params, torch.Tensor) else torch.tensor(dx.params)
             step = LQRStep(n, m, T, u_lower=self.u_lower, u_upper=self.u_upper, u_zero_I=self.u_zero_I,
                            true_cost=QuadCost(C, c), true_dynamics=dx, current_x=x, current_u=u,

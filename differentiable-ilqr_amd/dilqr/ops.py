@@ -1,6 +1,13 @@
 """Functional layer over the C-ABI: allocate outputs, launch on the current
 stream.  Every function here is one (or a few) libdilqr.so calls; nothing
 computes on the host.
+
+What the kernels take for a dynamics is resolved in one place: a Dynamics
+handle (model id, (n, m), and theta / F, f / the MLP descriptor), made by
+device_dynamics from a dynamics object or by Dynamics.of from the public
+functions' (model_id, theta, F, f).  Its three launches (rollout, linearise,
+line search) are the only call sites of those entry points; rollout,
+linearize, mlp_*, lqr_forward and mpc_solve_unfused all go through them.
 """
 import collections
 import os
@@ -16,31 +23,6 @@ def _f32(t):
     if t.dtype != torch.float32:
         raise TypeError(f"dilqr computes in fp32; got {t.dtype}")
     return t.detach().contiguous()
-
-
-def model_id_of(dx):
-    from .definitions import LinDx
-    if isinstance(dx, LinDx):
-        return N.MODEL_LINDX
-    mid = getattr(dx, "model_id", None)
-    if mid is None:
-        raise NotImplementedError(
-            "dilqr: dynamics must be a dilqr.env_dx model or a LinDx "
-            "(generic autograd/finite-difference dynamics are not on the HIP path)")
-    return mid
-
-
-def generic_model_id(dx):
-    """model_id_of, or None for a dynamics Module the HIP kernels do not model
-    (the caller then runs it in torch)."""
-    from .definitions import LinDx
-    if isinstance(dx, LinDx):
-        return N.MODEL_LINDX
-    return getattr(dx, "model_id", None)
-
-
-def theta_of(dx, like):
-    return dx._theta(like)
 
 
 class MlpModel:
@@ -73,16 +55,122 @@ class MlpModel:
             raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
 
 
-def _mlp(model_id, theta):
-    """The MlpModel when (model_id, theta) names one: the descriptor itself in
-    place of model_id, or MODEL_MLP with the descriptor as theta."""
-    if isinstance(model_id, MlpModel):
+class Dynamics:
+    """What the kernels take for one dynamics, resolved once per solve: the
+    model id, (n, m), and theta (an env_dx model), F / f (LinDx) or the
+    MlpModel (model_id MODEL_MLP, or the MlpModel in its place, with the
+    descriptor as theta or ignored).  The three launches write into buffers of
+    the caller, who has validated their shapes; T and B come from the buffers."""
+
+    def __init__(self, model_id, n, m, theta=None, F=None, f=None):
+        self.mlp = None
+        if isinstance(model_id, MlpModel):
+            model_id, theta = N.MODEL_MLP, model_id
+        if model_id == N.MODEL_MLP:
+            if not isinstance(theta, MlpModel):
+                raise TypeError("dilqr: MODEL_MLP needs an MlpModel (NNDynamics.device_model) as theta")
+            if (theta.n, theta.m) != (n, m):        # the kernels index the weights by n and m
+                raise ValueError(f"dilqr: MLP model is (n, m) = {(theta.n, theta.m)}; got (n, m) = {(n, m)}")
+            self.mlp, theta, F, f = theta, None, None, None
+        self.model_id, self.n, self.m = model_id, n, m
+        self.theta, self.F, self.f = theta, _f32(F), _f32(f)
+        # these line searches take the previous one's cost of the accepted
+        # candidate as the old cost (as the fused MPC kernel does); the others
+        # recompute it
+        self.carries_cost = model_id in (N.MODEL_PENDULUM, N.MODEL_CARTPOLE, N.MODEL_MLP)
+
+    @classmethod
+    def of(cls, model_id, theta, n, m, F=None, f=None):
+        """The handle for the public functions' (model_id, theta, F, f), (n, m)
+        being their buffers'; a handle in place of model_id is returned as it is
+        once its (n, m) are seen to be the same."""
+        if not isinstance(model_id, cls):
+            return cls(model_id, n, m, theta, F, f)
+        if (model_id.n, model_id.m) != (n, m):
+            raise ValueError(f"dilqr: dynamics is (n, m) = {(model_id.n, model_id.m)}; the operands have {(n, m)}")
         return model_id
-    if model_id == N.MODEL_MLP:
-        if not isinstance(theta, MlpModel):
-            raise TypeError("dilqr: MODEL_MLP needs an MlpModel (NNDynamics.device_model) as theta")
-        return theta
-    return None
+
+    def _head(self, T, B):
+        if self.mlp is not None:
+            return self.n, self.m, T, B, self.mlp.desc
+        return self.model_id, self.n, self.m, T, B, N.ptr(self.theta), N.ptr(self.F), N.ptr(self.f)
+
+    def rollout(self, x_init, u, x_out):
+        """util.get_traj (util.py:104-127): x_out [T,B,n] from x_init and u [T,B,m]."""
+        T, B = u.shape[:2]
+        N.call("dilqr_mlp_rollout_f32" if self.mlp is not None else "dilqr_rollout_f32", *self._head(T, B),
+               N.ptr(x_init), N.ptr(u), N.ptr(x_out), N.stream(u.device))
+
+    def linearize(self, x, u):
+        """F [T-1,B,n,n+m], f [T-1,B,n] at (x, u); a LinDx returns its own."""
+        if self.model_id == N.MODEL_LINDX:
+            return self.F, self.f
+        T, B = x.shape[:2]
+        F = torch.empty(max(T - 1, 0), B, self.n, self.n + self.m, device=x.device)
+        f = torch.empty(max(T - 1, 0), B, self.n, device=x.device)
+        if self.mlp is None:
+            N.call("dilqr_linearize_f32", self.model_id, T, B, N.ptr(self.theta), N.ptr(x), N.ptr(u), N.ptr(F),
+                   N.ptr(f), N.stream(x.device))
+        elif T > 1 and B > 0:                       # the MLP entry point is not handed empty outputs
+            N.call("dilqr_mlp_linearize_f32", self.n, self.m, T, B, self.mlp.desc, N.ptr(x), N.ptr(u), N.ptr(F),
+                   N.ptr(f), N.stream(x.device))
+        return F, f
+
+    def line_search(self, x_init, C, c, x, u, K, k, bounds, zI, decay, max_ls, x_out, u_out, cost, du_sq, alpha,
+                    old_cost=None):
+        """lqr_forward (lqr_step_explicit.py:166-263) from (x, u) with gains K, k
+        into x_out, u_out, cost [B], du_sq [T,m,B] (first pass), alpha [B]
+        (final pass); old_cost [B]: the cost of (x, u) when the caller has it."""
+        T, B = x.shape[:2]
+        N.call("dilqr_mlp_lqr_forward_f32" if self.mlp is not None else "dilqr_lqr_forward_f32", *self._head(T, B),
+               N.ptr(x_init), N.ptr(C), N.ptr(c), N.ptr(x), N.ptr(u), N.ptr(K), N.ptr(k), bounds, N.ptr(zI),
+               float(decay), int(max_ls), N.ptr(x_out), N.ptr(u_out), N.ptr(cost), N.ptr(du_sq), N.ptr(alpha),
+               N.ptr(old_cost), N.stream(x.device))
+
+
+def device_dynamics(dx, like, env=True, mlp=True):
+    """The Dynamics handle of a dynamics object for tensors like `like`: a LinDx
+    or an env_dx model (with env; theta is left out when like is None), or a
+    Module with a device model for GPU fp32 tensors (with mlp:
+    NNDynamics.device_model).  None for a Module the kernels do not model, or
+    of a kind the caller did not ask for (it then runs in torch)."""
+    from .definitions import LinDx
+    if isinstance(dx, LinDx):
+        if not env:
+            return None
+        n = dx.F.shape[-2]
+        return Dynamics(N.MODEL_LINDX, n, dx.F.shape[-1] - n, F=dx.F,
+                        f=None if dx.f is None or dx.f.nelement() == 0 else dx.f)
+    mid = getattr(dx, "model_id", None)
+    if mid is not None:
+        if not env:
+            return None
+        return Dynamics(mid, dx.n_state, dx.n_ctrl, theta=None if like is None else dx._theta(like))
+    make = getattr(dx, "device_model", None)
+    if not mlp or make is None or not like.is_cuda or like.dtype != torch.float32:
+        return None
+    md = make(like)
+    return None if md is None else Dynamics(md, md.n, md.m)
+
+
+def generic_model_id(dx):
+    """The model id of a LinDx or an env_dx model, or None for a dynamics Module
+    that is neither (the caller then runs it in torch, or on its device model)."""
+    dyn = device_dynamics(dx, None, mlp=False)
+    return None if dyn is None else dyn.model_id
+
+
+def model_id_of(dx):
+    mid = generic_model_id(dx)
+    if mid is None:
+        raise NotImplementedError(
+            "dilqr: dynamics must be a dilqr.env_dx model or a LinDx "
+            "(generic autograd/finite-difference dynamics are not on the HIP path)")
+    return mid
+
+
+def theta_of(dx, like):
+    return dx._theta(like)
 
 
 def _al16(t):
@@ -119,46 +207,31 @@ def mlp_rollout(mlp, x_init, u):
     x_init, u = _al16(_f32(x_init)), _al16(_f32(u))
     mlp.check(x_init, u[0])
     x = torch.empty(T, B, mlp.n, device=u.device)
-    N.call("dilqr_mlp_rollout_f32", mlp.n, mlp.m, T, B, mlp.desc, N.ptr(x_init), N.ptr(u), N.ptr(x),
-           N.stream(u.device))
+    Dynamics(mlp, mlp.n, mlp.m).rollout(x_init, u, x)
     return x
 
 
 def mlp_linearize(mlp, x, u):
     """MPC.linearize_dynamics ANALYTIC with grad_input (mpc.py:494-519):
     F [T-1,B,n,n+m], f [T-1,B,n] (empty, and nothing launched, at T = 1)."""
-    T, B, n = x.shape
     x, u = _al16(_f32(x)), _al16(_f32(u))
     mlp.check(x, u)
-    F = torch.empty(max(T - 1, 0), B, n, n + mlp.m, device=x.device)
-    f = torch.empty(max(T - 1, 0), B, n, device=x.device)
-    if T > 1 and B > 0:
-        N.call("dilqr_mlp_linearize_f32", mlp.n, mlp.m, T, B, mlp.desc, N.ptr(x), N.ptr(u), N.ptr(F), N.ptr(f),
-               N.stream(x.device))
-    return F, f
+    return Dynamics(mlp, mlp.n, mlp.m).linearize(x, u)
 
 
 def rollout(model_id, theta, x_init, u, F=None, f=None):
     """util.get_traj (util.py:104-127)."""
     T, B, m = u.shape
     n = x_init.shape[1]
-    x_init, u, F, f = _f32(x_init), _f32(u), _f32(F), _f32(f)
+    x_init, u = _f32(x_init), _f32(u)
     x = torch.empty(T, B, n, device=u.device)
-    N.call("dilqr_rollout_f32", model_id, n, m, T, B, N.ptr(theta), N.ptr(F), N.ptr(f), N.ptr(x_init), N.ptr(u),
-           N.ptr(x), N.stream(u.device))
+    Dynamics.of(model_id, theta, n, m, F, f).rollout(x_init, u, x)
     return x
 
 
 def linearize(model_id, theta, x, u):
     """MPC.linearize_dynamics ANALYTIC (mpc_explicit.py:516-546)."""
-    T, B, n = x.shape
-    m = u.shape[2]
-    x, u = _f32(x), _f32(u)
-    F = torch.empty(max(T - 1, 0), B, n, n + m, device=x.device)
-    f = torch.empty(max(T - 1, 0), B, n, device=x.device)
-    N.call("dilqr_linearize_f32", model_id, T, B, N.ptr(theta), N.ptr(x), N.ptr(u), N.ptr(F), N.ptr(f),
-           N.stream(x.device))
-    return F, f
+    return Dynamics.of(model_id, theta, x.shape[2], u.shape[2]).linearize(_f32(x), _f32(u))
 
 
 def zero_mask(u_zero_I, T, B, m, device):
@@ -229,38 +302,46 @@ def delta_u_rollout_bounds(u_lower, u_upper, u, delta_u):
     return lb.contiguous(), ub.contiguous()
 
 
+def delta_sweep(C, c, F, n, m, x, u, u_lower, u_upper, u_zero_I=None, delta_u=None, qp_total=False):
+    """The LQR step's Riccati sweep in delta space around (x, u): lqr_backward
+    with c_back fused into the kernel; with delta_u the box is relative to u
+    and clipped to +-delta_u (lqr_step_explicit.py:132-135) and c_back is formed
+    here; the u_zero_I mask applies only without bounds (the reference's pnqp
+    branch ignores it)."""
+    if delta_u is not None:
+        rlo, rhi = delta_u_sweep_bounds(u_lower, u_upper, u, delta_u)
+        return lqr_backward(C, c_back(C.detach(), c.detach(), x, u), F, n, m, u_lower=rlo, u_upper=rhi,
+                            qp_total=qp_total)
+    return lqr_backward(C, c, F, n, m, x=x, u=u, u_lower=u_lower, u_upper=u_upper,
+                        u_zero_I=u_zero_I if u_lower is None else None, qp_total=qp_total)
+
+
 def lqr_forward(model_id, theta, x_init, C, c, x, u, K, k, F=None, f=None, u_lower=None, u_upper=None,
                 u_zero_I=None, linesearch_decay=0.2, max_linesearch_iter=10):
     """lqr_forward (lqr_step_explicit.py:166-263): returns new_x, new_u, costs [B],
     du_sq [T,m,B] (first pass), alphas [B] (final pass).  An MlpModel in place
     of model_id (theta then ignored), or MODEL_MLP with it as theta, rolls out
-    the network (dilqr_mlp_lqr_forward_f32)."""
+    the network (the MLP entry point); a Dynamics handle in place of model_id
+    is taken as it is."""
     T, B, n = x.shape
     m = u.shape[2]
-    x_init, C, c, x, u, K, k, F, f = map(_f32, (x_init, C, c, x, u, K, k, F, f))
+    x_init, C, c, x, u, K, k = map(_f32, (x_init, C, c, x, u, K, k))
     bounds, keep = N.make_bounds(u_lower, u_upper)
     zI = zero_mask(u_zero_I, T, B, m, x.device)
     dev = x.device
     nx, nu = torch.empty_like(x), torch.empty_like(u)
     cost, alpha = torch.empty(B, device=dev), torch.empty(B, device=dev)
     du_sq = torch.empty(T, m, B, device=dev)
-    mlp = _mlp(model_id, theta)
-    if mlp is not None:
-        mlp.check(x, u)
+    dyn = Dynamics.of(model_id, theta, n, m, F, f)
+    if dyn.mlp is not None:
+        dyn.mlp.check(x, u)
         d = n + m
         if (tuple(x_init.shape), tuple(C.shape), tuple(c.shape), tuple(K.shape), tuple(k.shape)) != (
                 (B, n), (T, B, d, d), (T, B, d), (T, B, m, n), (T, B, m)):
             raise ValueError("dilqr: lqr_forward operands must be x_init [B,n], C [T,B,d,d], c [T,B,d], "
                              "K [T,B,m,n], k [T,B,m]")
-        N.call("dilqr_mlp_lqr_forward_f32", n, m, T, B, mlp.desc, N.ptr(x_init), N.ptr(C), N.ptr(c), N.ptr(x),
-               N.ptr(u), N.ptr(K), N.ptr(k), bounds, N.ptr(zI), float(linesearch_decay), int(max_linesearch_iter),
-               N.ptr(nx), N.ptr(nu), N.ptr(cost), N.ptr(du_sq), N.ptr(alpha), None, N.stream(dev))
-        del keep
-        return nx, nu, cost, du_sq, alpha
-    N.call("dilqr_lqr_forward_f32", model_id, n, m, T, B, N.ptr(theta), N.ptr(F), N.ptr(f), N.ptr(x_init),
-           N.ptr(C), N.ptr(c), N.ptr(x), N.ptr(u), N.ptr(K), N.ptr(k), bounds, N.ptr(zI),
-           float(linesearch_decay), int(max_linesearch_iter), N.ptr(nx), N.ptr(nu), N.ptr(cost), N.ptr(du_sq),
-           N.ptr(alpha), None, N.stream(dev))
+    dyn.line_search(x_init, C, c, x, u, K, k, bounds, zI, linesearch_decay, max_linesearch_iter, nx, nu, cost,
+                    du_sq, alpha)
     del keep
     return nx, nu, cost, du_sq, alpha
 
@@ -288,6 +369,24 @@ def quirk_norm(du_sq):
     out = torch.empty(B, device=du_sq.device)
     N.call("dilqr_quirk_norm_f32", T, m, B, N.ptr(du_sq), N.ptr(out), N.stream(du_sq.device))
     return out
+
+
+def _lim(not_improved_lim):
+    """not_improved_lim as the C-ABI's int (callers pass 10 ** 9 and more for "never")."""
+    return int(min(not_improved_lim, 2 ** 31 - 1))
+
+
+def expand_u_init(u_init, T, B, m, device, dtype=torch.float32):
+    """u_init on `device`, a [T,m] plan repeated over the batch as an expanded
+    view [T,B,m] (m = -1 keeps its last size).  What else the callers accept
+    differs and stays theirs: MPCSolve makes it contiguous and refuses any other
+    shape than [T,B,m] (ValueError); mpc_solve_unfused lets copy_ broadcast it
+    into its buffer; generic.solve keeps x_init's dtype, clones the expanded
+    view and takes a [T,B,m] tensor as it is."""
+    u0 = u_init.to(device=device, dtype=dtype)
+    if u0.ndimension() == 2:
+        u0 = u0.unsqueeze(1).expand(T, B, m)
+    return u0
 
 
 def grec_floats(n, m):
@@ -377,10 +476,7 @@ class MPCSolve:
     def _u_init(self, u_init):
         if u_init is None:
             return None
-        u0 = u_init.to(device=self.Xs.device, dtype=torch.float32)
-        if u0.ndimension() == 2:
-            u0 = u0.unsqueeze(1).expand(self.T, self.B, self.m)
-        u0 = u0.contiguous()
+        u0 = expand_u_init(u_init, self.T, self.B, self.m, self.Xs.device).contiguous()
         if tuple(u0.shape) != (self.T, self.B, self.m):
             raise ValueError(f"u_init: expected [T, B, m] = {(self.T, self.B, self.m)} or [T, m], got "
                              f"{tuple(u_init.shape)}")
@@ -415,7 +511,7 @@ class MPCSolve:
         u0 = self._u_init(u_init)
         N.call("dilqr_mpc_solve_small_f32", model_id, self.T, self.B, N.ptr(theta), N.ptr(x_init),
                None if u0 is None else N.ptr(u0), N.ptr(C), N.ptr(c), bounds, float(decay), int(max_ls),
-               int(iterations), float(best_cost_eps), float(eps), int(min(not_improved_lim, 2 ** 31 - 1)),
+               int(iterations), float(best_cost_eps), float(eps), _lim(not_improved_lim),
                self.state, N.stream(x_init.device))
         self._u0 = u0
         self.small = True
@@ -428,7 +524,7 @@ class MPCSolve:
             raise TypeError("iteration is the 0-based iteration index")
         N.call("dilqr_mpc_iterate_f32", model_id, self.T, self.B, N.ptr(theta), N.ptr(x_init), N.ptr(C),
                N.ptr(c), bounds, float(decay), int(max_ls), int(iteration), float(best_cost_eps), float(eps),
-               int(min(not_improved_lim, 2 ** 31 - 1)), self.state, N.stream(x_init.device))
+               _lim(not_improved_lim), self.state, N.stream(x_init.device))
         self.last_iteration = int(iteration)
 
     def iterate_range(self, model_id, theta, x_init, C, c, bounds, decay, max_ls, first, count, best_cost_eps, eps,
@@ -437,7 +533,7 @@ class MPCSolve:
         launches as iterate() for each)."""
         N.call("dilqr_mpc_iterate_range_f32", model_id, self.T, self.B, N.ptr(theta), N.ptr(x_init), N.ptr(C),
                N.ptr(c), bounds, float(decay), int(max_ls), int(first), int(count), float(best_cost_eps), float(eps),
-               int(min(not_improved_lim, 2 ** 31 - 1)), self.state, N.stream(x_init.device))
+               _lim(not_improved_lim), self.state, N.stream(x_init.device))
         if count > 0:
             self.last_iteration = int(first + count - 1)
 
@@ -530,57 +626,52 @@ def mpc_solve(model_id, theta, x_init, C, c, T, u_init=None, u_lower=None, u_upp
     if verbose > 0:
         _mpc_solve_logged(sv, model_id, theta, x_init, C, c, u_init, bounds, u_lower is None, lqr_iter, eps,
                           linesearch_decay, max_linesearch_iter, not_improved_lim, best_cost_eps)
-        del keep
-        x, u = sv.gather_best()
-        return x, u, sv.best_cost, sv.best_du, sv
-    if fixed:
+    elif fixed:
         sv.solve_fixed(model_id, theta, x_init, C, c, bounds, linesearch_decay, max_linesearch_iter, best_cost_eps,
                        u_init)
-        del keep
-        x, u = sv.gather_best()
-        return x, u, sv.best_cost, sv.best_du, sv
-    if B <= SMALL_BATCH_MAX and model_id in SMALL_BATCH_MODELS and lqr_iter >= 1:
+    elif B <= SMALL_BATCH_MAX and model_id in SMALL_BATCH_MODELS and lqr_iter >= 1:
         # the whole stop-rule loop in one launch (one workgroup holds the batch)
         sv.solve_small(model_id, theta, x_init, C, c, bounds, linesearch_decay, max_linesearch_iter, lqr_iter,
                        best_cost_eps, eps, not_improved_lim, u_init)
-        del keep
-        x, u = sv.gather_best()
-        return x, u, sv.best_cost, sv.best_du, sv
+    else:
+        _mpc_solve_polled(sv, model_id, theta, x_init, C, c, u_init, bounds, lqr_iter, eps, linesearch_decay,
+                          max_linesearch_iter, not_improved_lim, best_cost_eps, check_every)
+    del keep
+    x, u = sv.gather_best()
+    return x, u, sv.best_cost, sv.best_du, sv
+
+
+def _mpc_solve_polled(sv, model_id, theta, x_init, C, c, u_init, bounds, lqr_iter, eps, decay, max_ls,
+                      not_improved_lim, best_cost_eps, check_every):
+    """mpc_solve's stop-rule loop for a batch above one workgroup: runs of
+    check_every iterations per library call (iterations after a stop are
+    device no-ops).  The stop flag is polled without stalling the device:
+    after each run the control word is copied to pinned host memory behind an
+    event, and the host only waits for the copy of a run once POLL_AHEAD runs
+    are queued behind it — so the GPU never drains while the host looks (a
+    blocking poll every 8 iterations idled it once per poll), and at most
+    POLL_AHEAD runs of no-op launches follow a stop."""
     sv.begin(model_id, theta, x_init, u_init)
-    # runs of check_every iterations per library call (iterations after a stop
-    # are device no-ops).  The stop flag is polled without stalling the device:
-    # after each run the control word is copied to pinned host memory behind an
-    # event, and the host only waits for the copy of a run once POLL_AHEAD runs
-    # are queued behind it — so the GPU never drains while the host looks (a
-    # blocking poll every 8 iterations idled it once per poll), and at most
-    # POLL_AHEAD runs of no-op launches follow a stop.
     step = check_every if check_every else max(lqr_iter, 1)
     polls = collections.deque()
     n_polls = 0
     stream = torch.cuda.current_stream(x_init.device)
     for i0 in range(0, lqr_iter, step):
-        sv.iterate_range(model_id, theta, x_init, C, c, bounds, linesearch_decay, max_linesearch_iter, i0,
-                         min(step, lqr_iter - i0), best_cost_eps, eps, not_improved_lim)
+        sv.iterate_range(model_id, theta, x_init, C, c, bounds, decay, max_ls, i0, min(step, lqr_iter - i0),
+                         best_cost_eps, eps, not_improved_lim)
         if i0 + step >= lqr_iter:
-            break
+            return
         host = sv.poll_buffer(n_polls)            # a ring longer than the polls in flight
         n_polls += 1
         host.copy_(sv._ctrl_now(), non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(stream)
         polls.append((ev, host))
-        stopped = False
         while polls and (len(polls) > POLL_AHEAD or polls[0][0].query()):
             ev0, host0 = polls.popleft()
             ev0.synchronize()
             if int(host0[1]):
-                stopped = True
-                break
-        if stopped:
-            break
-    del keep
-    x, u = sv.gather_best()
-    return x, u, sv.best_cost, sv.best_du, sv
+                return
 
 
 def quad_traj_cost(x, u, C, c):
@@ -664,66 +755,43 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
     B, n = x_init.shape
     m = C.shape[-1] - n
     dev = x_init.device
-    x_init, C, c, F, f = _f32(x_init), _f32(C), _f32(c), _f32(F), _f32(f)
-    mlp = _mlp(model_id, theta)
-    if mlp is not None:
+    x_init, C, c = _f32(x_init), _f32(C), _f32(c)
+    dyn = Dynamics.of(model_id, theta, n, m, F, f)
+    if dyn.mlp is not None:
         # the network: the same four launches per iteration through the
         # dilqr_mlp_* entry points (rollout, linearise, line search)
-        if (mlp.n, mlp.m) != (n, m) or tuple(C.shape) != (T, B, n + m, n + m) or tuple(c.shape) != (T, B, n + m):
-            raise ValueError(f"dilqr: MLP model is (n, m) = {(mlp.n, mlp.m)}; got x_init {tuple(x_init.shape)}, "
+        if tuple(C.shape) != (T, B, n + m, n + m) or tuple(c.shape) != (T, B, n + m):
+            raise ValueError(f"dilqr: MLP model is (n, m) = {(n, m)}; got x_init {tuple(x_init.shape)}, "
                              f"C {tuple(C.shape)}, c {tuple(c.shape)} at T = {T}")
-        if x_init.device != mlp.device:
+        if x_init.device != dyn.mlp.device:
             raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
-        model_id = N.MODEL_MLP
     ws = MPCWorkspace(T, B, n, m, dev)
     if u_init is None:
         ws.ua.zero_()
     else:
-        u0 = u_init.to(device=dev, dtype=torch.float32)
-        if u0.ndimension() == 2:
-            u0 = u0.unsqueeze(1).expand(T, B, m)
-        ws.ua.copy_(u0)
+        ws.ua.copy_(expand_u_init(u_init, T, B, m, dev))
     s = N.stream(dev)
     zI = zero_mask(u_zero_I, T, B, m, dev)
-    if mlp is not None:
-        N.call("dilqr_mlp_rollout_f32", n, m, T, B, mlp.desc, N.ptr(x_init), N.ptr(ws.ua), N.ptr(ws.xa), s)
-    else:
-        N.call("dilqr_rollout_f32", model_id, n, m, T, B, N.ptr(theta), N.ptr(F), N.ptr(f), N.ptr(x_init),
-               N.ptr(ws.ua), N.ptr(ws.xa), s)
+    dyn.rollout(x_init, ws.ua, ws.xa)
     stats = None
     if verbose > 0:                        # the table rows, reduced on the stream (util.print_solve_log)
         stats = torch.zeros(max(lqr_iter, 1), 3, device=dev)
         initial = quad_traj_cost(ws.xa, ws.ua, C, c).mean()
+    bounds, keep = N.make_bounds(u_lower, u_upper)
+    lim = _lim(not_improved_lim)
     ran = 0
     for i in range(lqr_iter):
-        if model_id == N.MODEL_LINDX:
-            Fi, fi = F, f
-        elif mlp is not None:
-            Fi, fi = mlp_linearize(mlp, ws.xa, ws.ua)
-        else:
-            Fi, fi = linearize(model_id, theta, ws.xa, ws.ua)
+        Fi, _ = dyn.linearize(ws.xa, ws.ua)
         K, k, _ = lqr_backward(C, c, Fi, n, m, x=ws.xa, u=ws.ua, u_lower=u_lower, u_upper=u_upper,
                                u_zero_I=zI if u_lower is None else None)
-        bounds, keep = N.make_bounds(u_lower, u_upper)
         # from iteration 1 the old cost is the previous line search's value for
         # the accepted candidate (ws.cost), as the fused MPC kernel takes it
-        prev = (N.ptr(ws.cost) if i > 0 and model_id in (N.MODEL_PENDULUM, N.MODEL_CARTPOLE, N.MODEL_MLP)
-                else None)
-        if mlp is not None:
-            N.call("dilqr_mlp_lqr_forward_f32", n, m, T, B, mlp.desc, N.ptr(x_init), N.ptr(C), N.ptr(c),
-                   N.ptr(ws.xa), N.ptr(ws.ua), N.ptr(K), N.ptr(k), bounds, N.ptr(zI), float(linesearch_decay),
-                   int(max_linesearch_iter), N.ptr(ws.xb), N.ptr(ws.ub), N.ptr(ws.cost), N.ptr(ws.du_sq),
-                   N.ptr(ws.alpha), prev, s)
-        else:
-            N.call("dilqr_lqr_forward_f32", model_id, n, m, T, B, N.ptr(theta), N.ptr(F), N.ptr(f),
-                   N.ptr(x_init), N.ptr(C), N.ptr(c), N.ptr(ws.xa), N.ptr(ws.ua), N.ptr(K), N.ptr(k), bounds,
-                   N.ptr(zI), float(linesearch_decay), int(max_linesearch_iter), N.ptr(ws.xb), N.ptr(ws.ub),
-                   N.ptr(ws.cost), N.ptr(ws.du_sq), N.ptr(ws.alpha), prev, s)
-        N.call("dilqr_mpc_update_best_f32", n, m, T, B, int(i == 0), float(best_cost_eps), float(eps),
-               int(min(not_improved_lim, 2 ** 31 - 1)), N.ptr(ws.xb), N.ptr(ws.ub), N.ptr(ws.cost),
-               N.ptr(ws.du_sq), N.ptr(ws.fdn), N.ptr(ws.best_x), N.ptr(ws.best_u), N.ptr(ws.best_cost),
-               N.ptr(ws.best_du), N.ptr(ws.ctrl), s)
-        del keep
+        dyn.line_search(x_init, C, c, ws.xa, ws.ua, K, k, bounds, zI, linesearch_decay, max_linesearch_iter,
+                        ws.xb, ws.ub, ws.cost, ws.du_sq, ws.alpha,
+                        old_cost=ws.cost if i > 0 and dyn.carries_cost else None)
+        N.call("dilqr_mpc_update_best_f32", n, m, T, B, int(i == 0), float(best_cost_eps), float(eps), lim,
+               N.ptr(ws.xb), N.ptr(ws.ub), N.ptr(ws.cost), N.ptr(ws.du_sq), N.ptr(ws.fdn), N.ptr(ws.best_x),
+               N.ptr(ws.best_u), N.ptr(ws.best_cost), N.ptr(ws.best_du), N.ptr(ws.ctrl), s)
         if stats is not None:
             stats[i, 0] = ws.best_cost.mean()
             stats[i, 1] = ws.fdn.max()
@@ -737,6 +805,7 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
         # only every check_every iterations, like mpc_solve
         if check_every and (i + 1) % check_every == 0 and i + 1 < lqr_iter and int(ws.ctrl[1].item()):
             break
+    del keep
     if stats is not None:
         # k_mpc_control counts the iterations that ran (ctrl[0]) and stops counting
         # once the rule fired (ctrl[1])

@@ -192,3 +192,108 @@ def test_solve_routing(routed, monkeypatch):
     # and so does the switch
     monkeypatch.setattr(generic, "DEVICE_MLP", False)
     assert routed(dx, quad) == "torch"
+
+
+T_, B_, N_, M_ = 4, 3, 5, 1
+
+
+@pytest.fixture
+def step_routed(monkeypatch):
+    """One regular (non no-op) LQR step forward through each of its three
+    drivers, with the sweep (ops.lqr_backward) replaced by zero gains, the
+    device line search (ops.lqr_forward) by a stub that records the bounds it
+    was handed and ends the call, and the torch line search's first step
+    (generic.traj_cost) by another: route(...) tells which one the step
+    reached, and with which (u_lower, u_upper).  Every tensor is a FakeCuda."""
+    from dilqr import generic, lqr_step, lqr_step_explicit, ops
+
+    class FakeCuda(torch.Tensor):
+        is_cuda = True
+
+    def fake(*shape):
+        return torch.randn(*shape, generator=torch.Generator().manual_seed(sum(shape))).as_subclass(FakeCuda)
+
+    def sweep(C, c, F, n, m, **kw):
+        T, B = C.shape[:2]
+        return torch.zeros(T, B, m, n), torch.zeros(T, B, m), 0
+
+    seen = {}
+
+    def device(model_id, theta, x_init, C, c, x, u, K, k, F=None, f=None, u_lower=None, u_upper=None, **kw):
+        seen["bounds"] = (u_lower, u_upper)
+        raise _Taken("device")
+
+    def torch_loop(*a, **k):
+        raise _Taken("torch")
+
+    monkeypatch.setattr(ops, "lqr_backward", sweep)
+    monkeypatch.setattr(ops, "lqr_forward", device)
+    monkeypatch.setattr(generic, "traj_cost", torch_loop)
+
+    def route(driver, dx, cost, delta_u=None, lo=-1.0, hi=1.0):
+        d = N_ + M_
+        x_init, x, u = fake(B_, N_), fake(T_, B_, N_), fake(T_, B_, M_)
+        C, c, F = fake(T_, B_, d, d), fake(T_, B_, d), fake(T_ - 1, B_, N_, d)
+        seen.clear()
+        with pytest.raises(_Taken) as e:
+            if driver == "generic":
+                generic.lqr_step_forward(T_, N_, M_, x_init, C, c, F, x, u, cost, dx, lo, hi, delta_u, 0.2, 10)
+            else:
+                mod = {"classic": lqr_step, "explicit": lqr_step_explicit}[driver]
+                step = mod.LQRStep(N_, M_, T_, u_lower=lo, u_upper=hi, delta_u=delta_u, true_cost=cost,
+                                   true_dynamics=dx, current_x=x, current_u=u)
+                step(x_init, C, c, F)
+        return str(e.value), seen.get("bounds"), u
+
+    route.fake = fake
+    return route
+
+
+@pytest.mark.parametrize("driver", ["classic", "explicit", "generic"])
+def test_lqr_step_routing(step_routed, driver, monkeypatch):
+    """Which line search one LQR step takes, and with which rollout bounds.
+
+    Through both LQRStep factories an env_dx model or a LinDx with a QuadCost
+    takes the device line search, with or without delta_u.  generic.
+    lqr_step_forward called directly (the generic MPC loop's use of it) has
+    always run those dynamics in torch and sends only a device MLP to the
+    kernels; that difference between the drivers is part of today's routing
+    and is pinned here too.  A one-hidden-layer NNDynamics with a full QuadCost
+    and no delta_u takes the device line search through all three."""
+    from dilqr import generic, ops
+    from dilqr.definitions import LinDx, QuadCost
+    from dilqr.dynamics import NNDynamics
+    from dilqr.env_dx.cartpole import CartpoleDx
+    d = N_ + M_
+    fake = step_routed.fake
+    quad = QuadCost(fake(T_, B_, d, d), fake(T_, B_, d))
+    lin = LinDx(fake(T_ - 1, B_, N_, d), fake(T_ - 1, B_, N_))
+    nn = NNDynamics(N_, M_, hidden_sizes=[8])
+
+    def callable_cost(tau):
+        return (tau ** 2).sum(-1)
+
+    env_route = "device" if driver != "generic" else "torch"
+    for dx, delta_u, want in ((CartpoleDx(), None, env_route), (CartpoleDx(), 0.25, env_route),
+                              (lin, None, env_route), (lin, 0.25, env_route), (nn, None, "device")):
+        took, bounds, u = step_routed(driver, dx, quad, delta_u=delta_u)
+        assert took == want, (type(dx).__name__, delta_u)
+        if took == "device" and delta_u is None:
+            assert bounds == (-1.0, 1.0)
+        elif took == "device":
+            lo, hi = ops.delta_u_rollout_bounds(-1.0, 1.0, u, delta_u)
+            assert torch.equal(bounds[0], lo) and torch.equal(bounds[1], hi)
+    # unbounded: no bounds reach the line search
+    took, bounds, _ = step_routed(driver, CartpoleDx(), quad, lo=None, hi=None)
+    assert (took, bounds) == (env_route, (None, None) if env_route == "device" else None)
+    took, bounds, _ = step_routed(driver, nn, quad, lo=None, hi=None)
+    assert (took, bounds) == ("device", (None, None))
+    # everything else keeps the torch line search
+    assert step_routed(driver, nn, quad, delta_u=0.25)[0] == "torch"
+    assert step_routed(driver, nn, callable_cost)[0] == "torch"
+    assert step_routed(driver, NNDynamics(N_, M_, hidden_sizes=[8, 8]), quad)[0] == "torch"
+    assert step_routed(driver, CartpoleDx(), callable_cost)[0] == "torch"
+    # a QuadCost that is not the full [T,B,d,d] / [T,B,d] keeps the MLP in torch
+    assert step_routed(driver, nn, QuadCost(fake(d, d), fake(d)))[0] == "torch"
+    monkeypatch.setattr(generic, "DEVICE_MLP", False)
+    assert step_routed(driver, nn, quad)[0] == "torch"
