@@ -44,7 +44,7 @@ inline size_t mlp_lds_bytes(int, int, int) { return 0; }
 
 template <int N_, int M_, int ACT>
 struct Mlp {
-  static constexpr int N = N_, M = M_, D = N_ + M_;
+  static constexpr int N = N_, M = M_, D = N_ + M_, kAct = ACT;
   static constexpr bool kForwardJacobian = true;   // forward_jacobian(): one walk over the hidden units
   using Arg = MlpArg;
   int H;

@@ -129,7 +129,7 @@ using namespace dilqr;
 
 extern "C" {
 
-int dilqr_version(void) { return 10; }
+int dilqr_version(void) { return 11; }
 
 // hash of csrc/ + include/dilqr.h at build time (Makefile); _native checks it
 // against the tree so a stale prebuilt library cannot be loaded silently

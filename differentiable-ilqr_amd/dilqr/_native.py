@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must be imported first: libdilqr.so then binds to t
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DILQR_LIB", os.path.join(_HERE, "libdilqr.so"))
-ABI_VERSION = 10
+ABI_VERSION = 11
 _PKG = os.path.dirname(_HERE)          # differentiable-ilqr_amd/ (the Makefile's directory)
 
 MODEL_LINDX, MODEL_PENDULUM, MODEL_CARTPOLE, MODEL_ROCKET, MODEL_PENDULUM_COMPLEX = 0, 1, 2, 3, 4
@@ -97,6 +97,13 @@ SIGNATURES = {
     "dilqr_mlp_linearize_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp, _vp], _i),
     "dilqr_mlp_lqr_forward_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Bounds, _vp, _f, _i, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "dilqr_mlp_linearize_vjp_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp,
+                                     ctypes.c_size_t, _vp], _i),
+}
+# the entry points that return a size, not a status (SIGNATURES is the list of
+# those that return int or a string, which tests/test_abi.py reads off the header)
+SIZE_SIGNATURES = {
+    "dilqr_mlp_linearize_vjp_ws_bytes": ([_i, _i, _i, _i, _i, _i], ctypes.c_size_t),
 }
 
 _lib = None
@@ -128,7 +135,7 @@ def lib():
                 "`python __graft_entry__.py` (or `make -C differentiable-ilqr_amd`). "
                 "There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (args, res) in SIGNATURES.items():
+        for name, (args, res) in {**SIGNATURES, **SIZE_SIGNATURES}.items():
             fn = getattr(handle, name)
             fn.argtypes = args
             fn.restype = res

@@ -9,7 +9,9 @@ Riccati sweeps are the HIP kernel.  An NNDynamics with one hidden layer
 (sigmoid or relu) also has a device model (`device_model`, csrc/dilqr_mlp.h):
 dilqr.generic then runs its rollouts, ANALYTIC linearisation, line search and
 whole solves through the HIP MLP kernels, which read the module's weights in
-place; gradients into the weights still go through torch (final_step).
+place, and the gradient of a solve reaches the weights through a HIP backward
+of the linearisation (ops.mlp_linearize_diff, generic.DEVICE_MLP_VJP); any
+other NNDynamics keeps the torch graph through grad_input (final_step).
 """
 import torch
 import torch.nn.functional as Fn

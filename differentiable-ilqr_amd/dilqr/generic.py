@@ -14,7 +14,8 @@ reference's `torch.diag(alphas).mm(kt)` is O(B^2); here it is a broadcast),
 the best-iterate bookkeeping and stop rule follow mpc_explicit.py:262-299.
 One Module is not run by torch: an NNDynamics with a device model (one hidden
 layer, sigmoid or relu; NNDynamics.device_model) goes through the HIP MLP
-kernels — see DEVICE_MLP below.
+kernels, the gradient into its weights included — see DEVICE_MLP and
+DEVICE_MLP_VJP below.
 
 lqr_step_forward is the one regular forward of an LQR step: the LQRStep
 factories (lqr_step.py, lqr_step_explicit.py) call it too.  Whether its line
@@ -65,6 +66,11 @@ def quad_stage_cost(tau, C, c):
 # (csrc/tu_mlp.hip).  False restores the torch loop everywhere (tests and
 # tools/bench_nn_mpc.py run both on the same inputs).
 DEVICE_MLP = True
+# With DEVICE_MLP, the differentiable ANALYTIC linearisation of final_step (the
+# one place a solve's gradient reaches the network's weights) is the same
+# kernel with a HIP backward (ops.mlp_linearize_diff, csrc/tu_mlp_vjp.hip).
+# False keeps the torch graph through NNDynamics.grad_input for it.
+DEVICE_MLP_VJP = True
 
 
 def device_mlp(dynamics, like):
@@ -166,6 +172,12 @@ def linearize(mpc, x, u, dynamics, diff):
         if mlp is not None:
             # the network: value and grad_input's [R S] of every row in one kernel
             return ops.mlp_linearize(mlp, x.detach(), u.detach())
+    if gm == GradMethods.ANALYTIC and diff and mid is None and hasattr(dynamics, "grad_input") and DEVICE_MLP_VJP:
+        mlp = device_mlp(dynamics, x)
+        if mlp is not None:
+            # the same kernel, with the device VJP into the module's own parameters as its backward
+            fc1, fc2 = dynamics.fcs
+            return ops.mlp_linearize_diff(mlp, (fc1.weight, fc1.bias, fc2.weight, fc2.bias), x.detach(), u.detach())
     xs = x[:-1].detach().reshape(-1, n)
     us = u[:-1].detach().reshape(-1, m)
     if gm == GradMethods.ANALYTIC:
@@ -471,8 +483,10 @@ def final_step(mpc, x_init, cost, dx, x, u, classic):
     """The reference's closing no-op LQR step (mpc_explicit.py:302-325,
     mpc.py:299-318): linearise at the best iterate WITH gradients (the
     autograd linearisation / cost expansion graphs carry them to the dynamics'
-    and cost's parameters), then the no-op step whose backward is the classic
-    adjoint kernel (classic=True) or the DiLQR implicit backward."""
+    and cost's parameters; for a network with a device model the linearisation
+    and its backward are HIP kernels, DEVICE_MLP_VJP), then the no-op step whose
+    backward is the classic adjoint kernel (classic=True) or the DiLQR implicit
+    backward."""
     from .lqr_step import LQRStep as ClassicStep
     from .lqr_step_explicit import LQRStep as ExplicitStep
     T, n, m = mpc.T, mpc.n_state, mpc.n_ctrl

@@ -116,6 +116,17 @@ class Dynamics:
                    N.ptr(f), N.stream(x.device))
         return F, f
 
+    def linearize_vjp(self, x, u, gF, gf, dW1, db1, dW2, db2, max_waves=0):
+        """The gradient of linearize's F, f into the network's weights (the MLP
+        only) for incoming gF, gf (None = zeros), written into dW1 [H,n+m],
+        db1 [H], dW2 [n,H], db2 [n]; the workspace is allocated here."""
+        T, B = x.shape[:2]
+        nbytes = N.lib().dilqr_mlp_linearize_vjp_ws_bytes(self.n, self.m, T, B, self.mlp.H, int(max_waves))
+        ws = torch.empty(max(nbytes // 4, 1), device=x.device)
+        N.call("dilqr_mlp_linearize_vjp_f32", self.n, self.m, T, B, self.mlp.desc, N.ptr(x), N.ptr(u), N.ptr(gF),
+               N.ptr(gf), N.ptr(dW1), N.ptr(db1), N.ptr(dW2), N.ptr(db2), int(max_waves), N.ptr(ws), nbytes,
+               N.stream(x.device))
+
     def line_search(self, x_init, C, c, x, u, K, k, bounds, zI, decay, max_ls, x_out, u_out, cost, du_sq, alpha,
                     old_cost=None):
         """lqr_forward (lqr_step_explicit.py:166-263) from (x, u) with gains K, k
@@ -217,6 +228,72 @@ def mlp_linearize(mlp, x, u):
     x, u = _al16(_f32(x)), _al16(_f32(u))
     mlp.check(x, u)
     return Dynamics(mlp, mlp.n, mlp.m).linearize(x, u)
+
+
+def mlp_linearize_vjp(mlp, x, u, gF, gf, max_waves=0):
+    """The backward of mlp_linearize into the weights: (dW1 [H,n+m], db1 [H],
+    dW2 [n,H], db2 [n]) for gradients gF [T-1,B,n,n+m] on F and gf [T-1,B,n]
+    on f (None = zeros) at x [T,B,n], u [T,B,m]; two launches, no atomics, the
+    same bits on every run (csrc/tu_mlp_vjp.hip).  max_waves caps the groups of
+    waves the rows are dealt to (0: the library's default); zeros, and nothing
+    launched, at T = 1 or B = 0."""
+    x, u = _al16(_f32(x)), _al16(_f32(u))
+    if x.ndimension() != 3 or u.ndimension() != 3:
+        raise ValueError(f"dilqr: mlp_linearize_vjp takes x [T,B,n], u [T,B,m]; got {tuple(x.shape)}, {tuple(u.shape)}")
+    mlp.check(x, u)
+    if max_waves < 0:
+        raise ValueError("dilqr: max_waves must be >= 0")
+    T, B = x.shape[:2]
+    n, d, H = mlp.n, mlp.n + mlp.m, mlp.H
+    gF, gf = (None if g is None else _al16(_f32(g)) for g in (gF, gf))
+    for g, shape, name in ((gF, (max(T - 1, 0), B, n, d), "gF"), (gf, (max(T - 1, 0), B, n), "gf")):
+        if g is None:
+            continue
+        if tuple(g.shape) != shape:
+            raise ValueError(f"dilqr: {name} must be {shape}; got {tuple(g.shape)}")
+        if g.device != mlp.device:
+            raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
+    rows = max(T - 1, 0) * B
+    new = torch.zeros if rows == 0 else torch.empty
+    out = tuple(new(*s, device=x.device) for s in ((H, d), (H,), (n, H), (n,)))
+    if rows:
+        Dynamics(mlp, mlp.n, mlp.m).linearize_vjp(x, u, gF, gf, *out, max_waves=max_waves)
+    return out
+
+
+class _MlpLinearizeDiff(torch.autograd.Function):
+    """mlp_linearize with the gradient into the four parameters (W1, b1, W2,
+    b2: the storage the MlpModel points at): the linearisation kernel forward,
+    mlp_linearize_vjp backward.  x and u get no gradient."""
+
+    @staticmethod
+    def forward(ctx, mlp, x, u, W1, b1, W2, b2):
+        ctx.mlp = mlp
+        ctx.set_materialize_grads(False)
+        # saved so that an in-place update of a parameter between forward and
+        # backward is refused by autograd (the kernels read the live storage)
+        ctx.save_for_backward(x, u, W1, b1, W2, b2)
+        F, f = mlp_linearize(mlp, x, u)
+        return F, f
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gF, gf):
+        x, u = ctx.saved_tensors[:2]
+        grads = mlp_linearize_vjp(ctx.mlp, x, u, gF, gf)
+        return (None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
+
+
+def mlp_linearize_diff(mlp, params, x, u):
+    """mlp_linearize(mlp, x, u) whose F, f carry the gradient into params =
+    (W1, b1, W2, b2), the Parameters mlp was made from (NNDynamics.fcs); the
+    same bits as mlp_linearize.  Not differentiable twice, and not with respect
+    to x and u."""
+    params = tuple(params)
+    if len(params) != 4 or any(p.data_ptr() != t.data_ptr() or p.shape != t.shape
+                               for p, t in zip(params, mlp.tensors)):
+        raise ValueError("dilqr: mlp_linearize_diff takes the four parameters (W1, b1, W2, b2) the MlpModel reads")
+    return _MlpLinearizeDiff.apply(mlp, x.detach(), u.detach(), *params)
 
 
 def rollout(model_id, theta, x_init, u, F=None, f=None):

@@ -28,6 +28,8 @@
 #ifndef DILQR_H
 #define DILQR_H
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -73,7 +75,7 @@ typedef struct dilqr_bounds {
   const float* hi_t;             /* [T,B,m] or NULL                              */
 } dilqr_bounds;
 
-/* Library version (for the loader's sanity check): 10. */
+/* Library version (for the loader's sanity check): 11. */
 int dilqr_version(void);
 
 /* Build id: the first 16 hex digits of the sha256 of the sources the library
@@ -466,6 +468,40 @@ int dilqr_mlp_lqr_forward_f32(int n, int m, int T, int B, dilqr_mlp mlp, const f
                               float linesearch_decay, int max_linesearch_iter,
                               float* x_out, float* u_out, float* cost, float* du_sq,
                               float* alpha, const float* old_cost, void* stream);
+
+/* ---- gradient of the linearisation into the network's weights (ABI 11) ----- */
+/* The backward of dilqr_mlp_linearize_f32 with respect to W1, b1, W2, b2: the
+   vector-Jacobian product of MPC.linearize_dynamics ANALYTIC, mpc.py:494-519
+   (F = [R S] from NNDynamics.grad_input, dynamics.py:92-130, f = x' - F tau),
+   for incoming gradients gF on F and gf on f.  With tau = [x;u], z = W1 tau +
+   b1, a = act(z), g = act'(z) (as above), h = g (1 - 2a) for sigmoid and 0 for
+   relu (the reference's relu mask carries no gradient), o = gf and
+   Gb = gF - gf tau^T, per hidden unit j:
+     p_j = sum_i W2_ij o_i,  q_jk = sum_i W2_ij Gb_ik,  s_j = sum_k q_jk W1_jk,
+     zh_j = g_j p_j + h_j s_j,
+   and summed over the (T-1)*B rows:
+     dW2_ij = sum [o_i a_j + g_j sum_k Gb_ik W1_jk],   db2_i = sum o_i,
+     dW1_jk = sum [g_j q_jk + zh_j tau_k],             db1_j = sum zh_j.
+   x [T,B,n], u [T,B,m] (the rows t < T-1 are read); gF [T-1,B,n,n+m] and gf
+   [T-1,B,n], either may be NULL (= zeros); dW1 [H,n+m], db1 [H], dW2 [n,H],
+   db2 [n] are written, never accumulated into.  Two launches: the first sums
+   the rows on chip (one row per lane, 64-row chunks dealt round-robin to G
+   groups of waves, G = min(ceil(rows / 64), cap), cap = max_waves or the
+   library's default when 0) into a workspace of G slabs of P = H (n+m+1) + n H
+   + n floats; the second writes each output as the sum of its G partials in a
+   fixed order.  No atomics: the same inputs give the same bits.  The workspace
+   is the caller's (dilqr_mlp_linearize_vjp_ws_bytes = 4 G P bytes; 0 for sizes
+   the call refuses), 16-byte aligned, and needs no initialisation.
+   Errors as dilqr_mlp_linearize_f32, plus DILQR_E_ARG for a null or misaligned
+   output, a null, misaligned or too small workspace, or max_waves < 0.  With
+   T = 1 or B = 0 there are no rows: nothing is launched and the outputs are
+   not written, as for every dilqr_mlp_* call (the gradient is zero). */
+size_t dilqr_mlp_linearize_vjp_ws_bytes(int n, int m, int T, int B, int n_hidden,
+                                        int max_waves);
+int dilqr_mlp_linearize_vjp_f32(int n, int m, int T, int B, dilqr_mlp mlp, const float* x,
+                                const float* u, const float* gF, const float* gf,
+                                float* dW1, float* db1, float* dW2, float* db2,
+                                int max_waves, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
