@@ -18,7 +18,8 @@ ABI_VERSION = 11
 _PKG = os.path.dirname(_HERE)          # differentiable-ilqr_amd/ (the Makefile's directory)
 
 MODEL_LINDX, MODEL_PENDULUM, MODEL_CARTPOLE, MODEL_ROCKET, MODEL_PENDULUM_COMPLEX = 0, 1, 2, 3, 4
-MODEL_MLP = 5          # a one-hidden-layer network, described by an Mlp (the dilqr_mlp_* entry points)
+MODEL_MLP = 5          # a network, described by an Mlp (one hidden layer, the dilqr_mlp_* entry points)
+                       # or an Mlp2 (two, dilqr_mlp2_*)
 MLP_SIGMOID, MLP_RELU = 0, 1
 MLP_MAX_HIDDEN = 256   # DILQR_MLP_MAX_HIDDEN
 # (n, m) the one-lane-per-problem kernels are compiled for (csrc/dilqr_common.h DILQR_FOR_EACH_SHAPE)
@@ -39,7 +40,15 @@ class Mlp(ctypes.Structure):
                 ("W1", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("W2", ctypes.c_void_p), ("b2", ctypes.c_void_p)]
 
 
-CTRL_INTS = 8          # sizeof(dilqr_mpc_ctrl) / 4
+class Mlp2(ctypes.Structure):
+    """dilqr_mlp2: a two-hidden-layer network's sizes and weight pointers (include/dilqr.h)."""
+    _fields_ = [("n_hidden1", ctypes.c_int), ("n_hidden2", ctypes.c_int), ("activation", ctypes.c_int),
+                ("passthrough", ctypes.c_int),
+                ("W1", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("W2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+                ("W3", ctypes.c_void_p), ("b3", ctypes.c_void_p)]
+
+
+CTRL_INTS = 8         # sizeof(dilqr_mpc_ctrl) / 4
 
 
 class MpcState(ctypes.Structure):
@@ -99,6 +108,12 @@ SIGNATURES = {
                                    _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "dilqr_mlp_linearize_vjp_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp,
                                      ctypes.c_size_t, _vp], _i),
+    "dilqr_mlp2_dynamics_f32": ([_i, _i, _i, Mlp2, _vp, _vp, _vp, _vp], _i),
+    "dilqr_mlp2_linear_dyn_f32": ([_i, _i, _i, Mlp2, _vp, _vp, _vp, _vp], _i),
+    "dilqr_mlp2_rollout_f32": ([_i, _i, _i, _i, Mlp2, _vp, _vp, _vp, _vp], _i),
+    "dilqr_mlp2_linearize_f32": ([_i, _i, _i, _i, Mlp2, _vp, _vp, _vp, _vp, _vp], _i),
+    "dilqr_mlp2_lqr_forward_f32": ([_i, _i, _i, _i, Mlp2, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Bounds, _vp, _f, _i,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
 }
 # the entry points that return a size, not a status (SIGNATURES is the list of
 # those that return int or a string, which tests/test_abi.py reads off the header)

@@ -11,7 +11,10 @@ dilqr.generic then runs its rollouts, ANALYTIC linearisation, line search and
 whole solves through the HIP MLP kernels, which read the module's weights in
 place, and the gradient of a solve reaches the weights through a HIP backward
 of the linearisation (ops.mlp_linearize_diff, generic.DEVICE_MLP_VJP); any
-other NNDynamics keeps the torch graph through grad_input (final_step).
+other NNDynamics keeps the torch graph through grad_input (final_step).  One
+with two hidden layers has a device model too (`device_model(like, deep=True)`,
+csrc/dilqr_mlp2.h), used for the solve when generic.DEVICE_MLP_DEEP is on (it
+ships off); its gradient always goes through the torch graph.
 """
 import torch
 import torch.nn.functional as Fn
@@ -60,29 +63,34 @@ class NNDynamics(nn.Module):
             z = z + x
         return z.squeeze(0) if x_dim == 1 else z
 
-    def device_model(self, like):
+    def device_model(self, like, deep=False):
         """The network as the HIP MLP kernels take it (ops.MlpModel: sizes, flags
         and pointers to this module's own parameter storage — no copy, so an
         optimiser step is seen by the next solve), or None when the module is
         outside their envelope: more than one hidden layer, elu, a hidden width
         above N.MLP_MAX_HIDDEN, an (n, m) the one-lane kernels are not compiled
         for, parameters that are not fp32 / contiguous / 16-byte aligned, or
-        parameters on another device than `like`."""
+        parameters on another device than `like`.  With deep, a module with two
+        hidden layers inside the same envelope (both widths) gives its
+        ops.Mlp2Model (csrc/dilqr_mlp2.h); three or more still give None."""
         from . import _native as N
         from . import ops
-        if len(self.fcs) != 2 or self.activation not in ("sigmoid", "relu"):
+        layers = len(self.fcs) - 1
+        if layers not in ((1, 2) if deep else (1,)) or self.activation not in ("sigmoid", "relu"):
             return None
-        W1, b1, W2, b2 = self.fcs[0].weight, self.fcs[0].bias, self.fcs[1].weight, self.fcs[1].bias
-        H, d = W1.shape
-        n = W2.shape[0]
-        if (n, d - n) not in N.LANE_SHAPES or not 1 <= H <= N.MLP_MAX_HIDDEN:
+        params = [p for fc in self.fcs for p in (fc.weight, fc.bias)]
+        d = params[0].shape[1]
+        n = params[-2].shape[0]
+        widths = [fc.weight.shape[0] for fc in self.fcs[:-1]]
+        if (n, d - n) not in N.LANE_SHAPES or not all(1 <= H <= N.MLP_MAX_HIDDEN for H in widths):
             return None
-        for p in (W1, b1, W2, b2):
+        for p in params:
             if p is None or p.dtype != torch.float32 or not p.is_contiguous() or p.device != like.device \
                     or p.data_ptr() % 16:
                 return None
         act = N.MLP_SIGMOID if self.activation == "sigmoid" else N.MLP_RELU
-        return ops.MlpModel(n, d - n, act, self.passthrough, W1.detach(), b1.detach(), W2.detach(), b2.detach())
+        make = ops.MlpModel if layers == 1 else ops.Mlp2Model
+        return make(n, d - n, act, self.passthrough, *(p.detach() for p in params))
 
     def grad_input(self, x, u):
         """dynamics.py:92-130: R = d x'/d x, S = d x'/d u from the weights and the

@@ -15,7 +15,8 @@ the best-iterate bookkeeping and stop rule follow mpc_explicit.py:262-299.
 One Module is not run by torch: an NNDynamics with a device model (one hidden
 layer, sigmoid or relu; NNDynamics.device_model) goes through the HIP MLP
 kernels, the gradient into its weights included — see DEVICE_MLP and
-DEVICE_MLP_VJP below.
+DEVICE_MLP_VJP below; with DEVICE_MLP_DEEP (off by default) one with two
+hidden layers does too, except for that gradient.
 
 lqr_step_forward is the one regular forward of an LQR step: the LQRStep
 factories (lqr_step.py, lqr_step_explicit.py) call it too.  Whether its line
@@ -71,11 +72,18 @@ DEVICE_MLP = True
 # kernel with a HIP backward (ops.mlp_linearize_diff, csrc/tu_mlp_vjp.hip).
 # False keeps the torch graph through NNDynamics.grad_input for it.
 DEVICE_MLP_VJP = True
+# With DEVICE_MLP, a module with two hidden layers takes the same routes on its
+# own device model (ops.Mlp2Model, csrc/tu_mlp2.hip): rollout, the ANALYTIC
+# linearisation without gradient, the line search and the whole solve.  Its
+# gradient stays on the torch graph through grad_input whatever this says (no
+# device VJP exists for it).  Off: such a module runs in torch, as it always has.
+DEVICE_MLP_DEEP = False
 
 
 def device_mlp(dynamics, like):
-    """dynamics' ops.MlpModel for tensors like `like` (a GPU fp32 tensor), or None."""
-    dyn = ops.device_dynamics(dynamics, like, env=False, mlp=DEVICE_MLP)
+    """dynamics' ops.MlpModel (with DEVICE_MLP_DEEP possibly an ops.Mlp2Model)
+    for tensors like `like` (a GPU fp32 tensor), or None."""
+    dyn = ops.device_dynamics(dynamics, like, env=False, mlp=DEVICE_MLP, deep=DEVICE_MLP_DEEP)
     return None if dyn is None else dyn.mlp
 
 
@@ -174,8 +182,9 @@ def linearize(mpc, x, u, dynamics, diff):
             return ops.mlp_linearize(mlp, x.detach(), u.detach())
     if gm == GradMethods.ANALYTIC and diff and mid is None and hasattr(dynamics, "grad_input") and DEVICE_MLP_VJP:
         mlp = device_mlp(dynamics, x)
-        if mlp is not None:
+        if isinstance(mlp, ops.MlpModel):
             # the same kernel, with the device VJP into the module's own parameters as its backward
+            # (one hidden layer only: a two-layer model differentiates through grad_input below)
             fc1, fc2 = dynamics.fcs
             return ops.mlp_linearize_diff(mlp, (fc1.weight, fc1.bias, fc2.weight, fc2.bias), x.detach(), u.detach())
     xs = x[:-1].detach().reshape(-1, n)
@@ -284,7 +293,7 @@ def line_search_dynamics(true_cost, true_dynamics, x, delta_u, env_models):
       * any other Module -> torch."""
     if not isinstance(true_cost, QuadCost):
         return None
-    dyn = ops.device_dynamics(true_dynamics, x, env=env_models, mlp=DEVICE_MLP)
+    dyn = ops.device_dynamics(true_dynamics, x, env=env_models, mlp=DEVICE_MLP, deep=DEVICE_MLP_DEEP)
     if dyn is None or dyn.mlp is None:
         return dyn
     T, B, d = x.shape[0], x.shape[1], dyn.n + dyn.m

@@ -32,6 +32,7 @@ class MlpModel:
     the pointers alive.  Built by NNDynamics.device_model; passed to
     lqr_forward / mpc_solve_unfused in place of (model_id, theta)."""
     model_id = N.MODEL_MLP
+    entry = "dilqr_mlp_"                # its entry points: entry + "rollout_f32", ...
 
     def __init__(self, n, m, activation, passthrough, W1, b1, W2, b2):
         H = W1.shape[0]
@@ -55,25 +56,57 @@ class MlpModel:
             raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
 
 
+class Mlp2Model:
+    """A two-hidden-layer network as the dilqr_mlp2_* entry points take it
+    (csrc/dilqr_mlp2.h): the dilqr_mlp2 descriptor over the module's own
+    parameter storage, plus (n, m) and the tensors that keep the pointers
+    alive.  Built by NNDynamics.device_model(like, deep=True); stands wherever
+    an MlpModel does, except the weight gradient (mlp_linearize_vjp), which
+    exists for one hidden layer only."""
+    model_id = N.MODEL_MLP
+    entry = "dilqr_mlp2_"
+
+    def __init__(self, n, m, activation, passthrough, W1, b1, W2, b2, W3, b3):
+        H1, H2 = W1.shape[0], W2.shape[0]
+        if (n, m) not in N.LANE_SHAPES or not (1 <= H1 <= N.MLP_MAX_HIDDEN and 1 <= H2 <= N.MLP_MAX_HIDDEN):
+            raise ValueError(f"dilqr: no MLP kernels for (n, m) = {(n, m)}, (H1, H2) = {(H1, H2)}")
+        self.tensors = (W1, b1, W2, b2, W3, b3)
+        if tuple(tuple(t.shape) for t in self.tensors) != ((H1, n + m), (H1,), (H2, H1), (H2,), (n, H2), (n,)):
+            raise ValueError("dilqr: MLP weights must be W1 [H1,n+m], b1 [H1], W2 [H2,H1], b2 [H2], W3 [n,H2], b3 [n]")
+        for t in self.tensors:
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != W1.device or t.data_ptr() % 16:
+                raise ValueError("dilqr: MLP weights must be fp32, contiguous, 16-byte aligned, on one device")
+        self.n, self.m, self.H1, self.H2, self.device = n, m, H1, H2, W1.device
+        self.desc = N.Mlp2(H1, H2, int(activation), int(bool(passthrough)), *(t.data_ptr() for t in self.tensors))
+
+    check = MlpModel.check
+
+
+MLP_MODELS = (MlpModel, Mlp2Model)
+
+
 class Dynamics:
     """What the kernels take for one dynamics, resolved once per solve: the
     model id, (n, m), and theta (an env_dx model), F / f (LinDx) or the
-    MlpModel (model_id MODEL_MLP, or the MlpModel in its place, with the
-    descriptor as theta or ignored).  The three launches write into buffers of
-    the caller, who has validated their shapes; T and B come from the buffers."""
+    MlpModel / Mlp2Model (model_id MODEL_MLP, or the model in its place, with
+    the descriptor as theta or ignored).  The three launches write into buffers
+    of the caller, who has validated their shapes; T and B come from the
+    buffers."""
 
     def __init__(self, model_id, n, m, theta=None, F=None, f=None):
         self.mlp = None
-        if isinstance(model_id, MlpModel):
+        if isinstance(model_id, MLP_MODELS):
             model_id, theta = N.MODEL_MLP, model_id
         if model_id == N.MODEL_MLP:
-            if not isinstance(theta, MlpModel):
-                raise TypeError("dilqr: MODEL_MLP needs an MlpModel (NNDynamics.device_model) as theta")
+            if not isinstance(theta, MLP_MODELS):
+                raise TypeError("dilqr: MODEL_MLP needs an MlpModel or Mlp2Model (NNDynamics.device_model) as theta")
             if (theta.n, theta.m) != (n, m):        # the kernels index the weights by n and m
                 raise ValueError(f"dilqr: MLP model is (n, m) = {(theta.n, theta.m)}; got (n, m) = {(n, m)}")
             self.mlp, theta, F, f = theta, None, None, None
         self.model_id, self.n, self.m = model_id, n, m
         self.theta, self.F, self.f = theta, _f32(F), _f32(f)
+        # the family of entry points the three launches call
+        self._entry = "dilqr_" if self.mlp is None else self.mlp.entry
         # these line searches take the previous one's cost of the accepted
         # candidate as the old cost (as the fused MPC kernel does); the others
         # recompute it
@@ -98,7 +131,7 @@ class Dynamics:
     def rollout(self, x_init, u, x_out):
         """util.get_traj (util.py:104-127): x_out [T,B,n] from x_init and u [T,B,m]."""
         T, B = u.shape[:2]
-        N.call("dilqr_mlp_rollout_f32" if self.mlp is not None else "dilqr_rollout_f32", *self._head(T, B),
+        N.call(self._entry + "rollout_f32", *self._head(T, B),
                N.ptr(x_init), N.ptr(u), N.ptr(x_out), N.stream(u.device))
 
     def linearize(self, x, u):
@@ -112,7 +145,7 @@ class Dynamics:
             N.call("dilqr_linearize_f32", self.model_id, T, B, N.ptr(self.theta), N.ptr(x), N.ptr(u), N.ptr(F),
                    N.ptr(f), N.stream(x.device))
         elif T > 1 and B > 0:                       # the MLP entry point is not handed empty outputs
-            N.call("dilqr_mlp_linearize_f32", self.n, self.m, T, B, self.mlp.desc, N.ptr(x), N.ptr(u), N.ptr(F),
+            N.call(self._entry + "linearize_f32", self.n, self.m, T, B, self.mlp.desc, N.ptr(x), N.ptr(u), N.ptr(F),
                    N.ptr(f), N.stream(x.device))
         return F, f
 
@@ -133,18 +166,19 @@ class Dynamics:
         into x_out, u_out, cost [B], du_sq [T,m,B] (first pass), alpha [B]
         (final pass); old_cost [B]: the cost of (x, u) when the caller has it."""
         T, B = x.shape[:2]
-        N.call("dilqr_mlp_lqr_forward_f32" if self.mlp is not None else "dilqr_lqr_forward_f32", *self._head(T, B),
+        N.call(self._entry + "lqr_forward_f32", *self._head(T, B),
                N.ptr(x_init), N.ptr(C), N.ptr(c), N.ptr(x), N.ptr(u), N.ptr(K), N.ptr(k), bounds, N.ptr(zI),
                float(decay), int(max_ls), N.ptr(x_out), N.ptr(u_out), N.ptr(cost), N.ptr(du_sq), N.ptr(alpha),
                N.ptr(old_cost), N.stream(x.device))
 
 
-def device_dynamics(dx, like, env=True, mlp=True):
+def device_dynamics(dx, like, env=True, mlp=True, deep=False):
     """The Dynamics handle of a dynamics object for tensors like `like`: a LinDx
     or an env_dx model (with env; theta is left out when like is None), or a
     Module with a device model for GPU fp32 tensors (with mlp:
-    NNDynamics.device_model).  None for a Module the kernels do not model, or
-    of a kind the caller did not ask for (it then runs in torch)."""
+    NNDynamics.device_model; with deep its two-hidden-layer model too).  None
+    for a Module the kernels do not model, or of a kind the caller did not ask
+    for (it then runs in torch)."""
     from .definitions import LinDx
     if isinstance(dx, LinDx):
         if not env:
@@ -160,7 +194,7 @@ def device_dynamics(dx, like, env=True, mlp=True):
     make = getattr(dx, "device_model", None)
     if not mlp or make is None or not like.is_cuda or like.dtype != torch.float32:
         return None
-    md = make(like)
+    md = make(like, deep=True) if deep else make(like)
     return None if md is None else Dynamics(md, md.n, md.m)
 
 
@@ -191,12 +225,14 @@ def _al16(t):
 
 
 def mlp_dynamics(mlp, x, u):
-    """NNDynamics.forward (dynamics.py:66-90) for rows x [N,n], u [N,m]."""
+    """NNDynamics.forward (dynamics.py:66-90) for rows x [N,n], u [N,m]; mlp an
+    MlpModel or an Mlp2Model, here and in mlp_linear_dyn, mlp_rollout and
+    mlp_linearize."""
     x, u = _al16(_f32(x)), _al16(_f32(u))
     mlp.check(x, u)
     rows = x.shape[0]
     out = torch.empty(rows, mlp.n, device=x.device)
-    N.call("dilqr_mlp_dynamics_f32", mlp.n, mlp.m, rows, mlp.desc, N.ptr(x), N.ptr(u), N.ptr(out),
+    N.call(mlp.entry + "dynamics_f32", mlp.n, mlp.m, rows, mlp.desc, N.ptr(x), N.ptr(u), N.ptr(out),
            N.stream(x.device))
     return out
 
@@ -207,7 +243,7 @@ def mlp_linear_dyn(mlp, x, u):
     mlp.check(x, u)
     rows = x.shape[0]
     D = torch.empty(rows, mlp.n, mlp.n + mlp.m, device=x.device)
-    N.call("dilqr_mlp_linear_dyn_f32", mlp.n, mlp.m, rows, mlp.desc, N.ptr(x), N.ptr(u), N.ptr(D),
+    N.call(mlp.entry + "linear_dyn_f32", mlp.n, mlp.m, rows, mlp.desc, N.ptr(x), N.ptr(u), N.ptr(D),
            N.stream(x.device))
     return D
 
@@ -237,6 +273,8 @@ def mlp_linearize_vjp(mlp, x, u, gF, gf, max_waves=0):
     same bits on every run (csrc/tu_mlp_vjp.hip).  max_waves caps the groups of
     waves the rows are dealt to (0: the library's default); zeros, and nothing
     launched, at T = 1 or B = 0."""
+    if not isinstance(mlp, MlpModel):
+        raise TypeError("dilqr: mlp_linearize_vjp is built for the one-hidden-layer MlpModel only")
     x, u = _al16(_f32(x)), _al16(_f32(u))
     if x.ndimension() != 3 or u.ndimension() != 3:
         raise ValueError(f"dilqr: mlp_linearize_vjp takes x [T,B,n], u [T,B,m]; got {tuple(x.shape)}, {tuple(u.shape)}")
@@ -396,10 +434,10 @@ def delta_sweep(C, c, F, n, m, x, u, u_lower, u_upper, u_zero_I=None, delta_u=No
 def lqr_forward(model_id, theta, x_init, C, c, x, u, K, k, F=None, f=None, u_lower=None, u_upper=None,
                 u_zero_I=None, linesearch_decay=0.2, max_linesearch_iter=10):
     """lqr_forward (lqr_step_explicit.py:166-263): returns new_x, new_u, costs [B],
-    du_sq [T,m,B] (first pass), alphas [B] (final pass).  An MlpModel in place
-    of model_id (theta then ignored), or MODEL_MLP with it as theta, rolls out
-    the network (the MLP entry point); a Dynamics handle in place of model_id
-    is taken as it is."""
+    du_sq [T,m,B] (first pass), alphas [B] (final pass).  An MlpModel or
+    Mlp2Model in place of model_id (theta then ignored), or MODEL_MLP with it as
+    theta, rolls out the network (its own entry point); a Dynamics handle in
+    place of model_id is taken as it is."""
     T, B, n = x.shape
     m = u.shape[2]
     x_init, C, c, x, u, K, k = map(_f32, (x_init, C, c, x, u, K, k))
@@ -821,8 +859,9 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
     iteration.  u_zero_I [T,B,m] (bool): controls held at zero — the sweep's
     masked solve when unconstrained (lqr_step_explicit.py:98-129; with bounds
     the reference's pnqp branch ignores the mask) and zeroed in every rollout
-    before the clamp (199-200).  An MlpModel (NNDynamics.device_model) in place
-    of model_id, or MODEL_MLP with it as theta, runs the loop on the network.
+    before the clamp (199-200).  An MlpModel or Mlp2Model (NNDynamics.
+    device_model) in place of model_id, or MODEL_MLP with it as theta, runs the
+    loop on the network; which of the two it is only the handle knows.
 
     The host polls the stop flag every `check_every` iterations: up to
     check_every - 1 iterations after the stop rule fired still run their
@@ -836,7 +875,7 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
     dyn = Dynamics.of(model_id, theta, n, m, F, f)
     if dyn.mlp is not None:
         # the network: the same four launches per iteration through the
-        # dilqr_mlp_* entry points (rollout, linearise, line search)
+        # dilqr_mlp_* / dilqr_mlp2_* entry points (rollout, linearise, line search)
         if tuple(C.shape) != (T, B, n + m, n + m) or tuple(c.shape) != (T, B, n + m):
             raise ValueError(f"dilqr: MLP model is (n, m) = {(n, m)}; got x_init {tuple(x_init.shape)}, "
                              f"C {tuple(C.shape)}, c {tuple(c.shape)} at T = {T}")

@@ -503,6 +503,51 @@ int dilqr_mlp_linearize_vjp_f32(int n, int m, int T, int B, dilqr_mlp mlp, const
                                 float* dW1, float* db1, float* dW2, float* db2,
                                 int max_waves, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- learned dynamics: a two-hidden-layer network --------------------------- */
+/* The reference's NNDynamics (dynamics.py:15-130) with len(hidden_sizes) == 2
+   (the [H, H] of its IL experiment, il_exp.py:123):
+     x' = W3 act(W2 act(W1 [x;u] + b1) + b2) + b3   (+ x with passthrough),
+   and the Jacobian grad_input chains, W3 D2 W2 D1 W1 (+ I on the state block),
+   D = diag(act') formed from the activation as above.  act, the weights'
+   storage (torch's nn.Linear layouts, read in place: W1 [H1, n+m], b1 [H1],
+   W2 [H2, H1], b2 [H2], W3 [n, H2], b3 [n]; fp32, contiguous, 16-byte aligned),
+   the (n, m) and the one-row-per-lane mapping are those of dilqr_mlp; both
+   widths are in [1, DILQR_MLP_MAX_HIDDEN].  Every launch keeps the first
+   layer's activations in 256 * n_hidden1 bytes of LDS per 64 rows.
+   The five entry points take the arguments of their dilqr_mlp_* counterparts
+   and return the same errors, all before any launch: DILQR_E_ARG for a null or
+   misaligned pointer or a bad size, DILQR_E_SHAPE for an unsupported (n, m) or
+   a width outside [1, DILQR_MLP_MAX_HIDDEN], DILQR_E_MODE for an unknown
+   activation.  There is no weight-gradient entry point for this model. */
+typedef struct dilqr_mlp2 {
+  int n_hidden1;                 /* H1                                            */
+  int n_hidden2;                 /* H2                                            */
+  int activation;                /* DILQR_MLP_*                                   */
+  int passthrough;               /* != 0: x' += x, and I on the Jacobian's state block */
+  const float* W1;               /* [H1, n+m]  fcs[0].weight                      */
+  const float* b1;               /* [H1]       fcs[0].bias                        */
+  const float* W2;               /* [H2, H1]   fcs[1].weight                      */
+  const float* b2;               /* [H2]       fcs[1].bias                        */
+  const float* W3;               /* [n, H2]    fcs[2].weight                      */
+  const float* b3;               /* [n]        fcs[2].bias                        */
+} dilqr_mlp2;
+
+int dilqr_mlp2_dynamics_f32(int n, int m, int N, dilqr_mlp2 mlp, const float* x,
+                            const float* u, float* out, void* stream);
+int dilqr_mlp2_linear_dyn_f32(int n, int m, int N, dilqr_mlp2 mlp, const float* x,
+                              const float* u, float* D, void* stream);
+int dilqr_mlp2_rollout_f32(int n, int m, int T, int B, dilqr_mlp2 mlp, const float* x_init,
+                           const float* u, float* x_out, void* stream);
+int dilqr_mlp2_linearize_f32(int n, int m, int T, int B, dilqr_mlp2 mlp, const float* x,
+                             const float* u, float* F, float* f, void* stream);
+int dilqr_mlp2_lqr_forward_f32(int n, int m, int T, int B, dilqr_mlp2 mlp, const float* x_init,
+                               const float* C, const float* c, const float* x,
+                               const float* u, const float* K, const float* k,
+                               dilqr_bounds bounds, const unsigned char* u_zero_I,
+                               float linesearch_decay, int max_linesearch_iter,
+                               float* x_out, float* u_out, float* cost, float* du_sq,
+                               float* alpha, const float* old_cost, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

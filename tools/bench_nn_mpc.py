@@ -9,9 +9,11 @@ generic.DEVICE_MLP = False is the torch loop (the path before the MLP kernels
 existed).  Per batch and arm: warm-up solves, then repeated solves timed with
 device events, the two arms alternating; median, min and max are printed, and
 the costs of the two arms are compared.  Then the linearisation kernel alone
-at the largest batch, with its bytes and FLOPs per row.
+at the largest batch, with its bytes and FLOPs per row.  --hidden 64,64 takes a
+network with two hidden layers instead: the device arm then also turns
+generic.DEVICE_MLP_DEEP on (csrc/tu_mlp2.hip), the torch arm is the same loop.
 
-    python tools/bench_nn_mpc.py [--batches 32,4096,65536] [--out FILE]
+    python tools/bench_nn_mpc.py [--batches 32,4096,65536] [--hidden 64,64] [--out FILE]
 """
 import argparse
 import os
@@ -77,17 +79,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--budget", type=float, default=60.0, help="seconds of timed solves per batch and arm")
+    ap.add_argument("--hidden", default=str(HIDDEN), help="hidden widths: one (default) or two, as 64,64")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    hidden = [int(h) for h in args.hidden.split(",")]
+    if len(hidden) not in (1, 2):
+        sys.exit("bench_nn_mpc: --hidden takes one or two widths")
+    deep = len(hidden) == 2
     if not torch.cuda.is_available():
         sys.exit("bench_nn_mpc: needs a GPU (no CPU timing)")
     from dilqr import QuadCost, generic, ops
     from dilqr.dynamics import NNDynamics
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    dx = NNDynamics(N_STATE, N_CTRL, hidden_sizes=[HIDDEN], activation="sigmoid").to(dev)
+    dx = NNDynamics(N_STATE, N_CTRL, hidden_sizes=hidden, activation="sigmoid").to(dev)
     lines = [f"# bench_nn_mpc  commit {commit()}  lib {os.environ.get('DILQR_LIB', 'dilqr/libdilqr.so')}",
-             f"# NNDynamics({N_STATE},{N_CTRL},[{HIDDEN}],sigmoid) T={T} lqr_iter={LQR_ITER} fixed-count, u in [-1,1], "
+             f"# NNDynamics({N_STATE},{N_CTRL},{hidden},sigmoid) T={T} lqr_iter={LQR_ITER} fixed-count, u in [-1,1], "
              f"dense SPD cost; one mpc.MPC.forward under no_grad; device events; ms",
              f"# {torch.cuda.get_device_name(0)}  torch {torch.__version__}",
              "B        arm     n   median_ms      min_ms      max_ms   speedup   max_rel_cost_diff"]
@@ -98,12 +105,17 @@ def main():
 
     for s in lines:
         print(s, flush=True)
+    def arm(flag):
+        # the device arm: the MLP route on, for two hidden layers its deep switch too
+        generic.DEVICE_MLP = flag
+        generic.DEVICE_MLP_DEEP = flag and deep
+
     for B in [int(b) for b in args.batches.split(",")]:
         x0, C, c = problem(B, dev)
         cost, mpc = QuadCost(C, c), solver(B)
         times, costs = {True: [], False: []}, {}
         for flag in (True, False):
-            generic.DEVICE_MLP = flag
+            arm(flag)
             for _ in range(args.warmup if flag else 1):
                 timed_solve(mpc, x0, cost, dx)
         spent = {True: 0.0, False: 0.0}
@@ -111,12 +123,13 @@ def main():
             for flag in (True, False):
                 if r >= 3 and spent[flag] > args.budget:
                     continue
-                generic.DEVICE_MLP = flag
+                arm(flag)
                 t0 = time.perf_counter()
                 ms, cs = timed_solve(mpc, x0, cost, dx)
                 spent[flag] += time.perf_counter() - t0
                 times[flag].append(ms)
                 costs[flag] = cs
+        arm(False)
         generic.DEVICE_MLP = True
         rel = float(((costs[True] - costs[False]).abs() / costs[False].abs().clamp(min=1.0)).max())
         med = {f: statistics.median(times[f]) for f in times}
@@ -128,7 +141,7 @@ def main():
         torch.cuda.empty_cache()
     # the linearisation kernel alone at the largest batch
     B = max(int(b) for b in args.batches.split(","))
-    md = dx.device_model(torch.zeros(1, device=dev))
+    md = dx.device_model(torch.zeros(1, device=dev), deep=deep)
     g = torch.Generator().manual_seed(5)
     x = torch.randn(T, B, N_STATE, generator=g).to(dev)
     u = torch.randn(T, B, N_CTRL, generator=g).clamp(-1, 1).to(dev)
@@ -142,9 +155,17 @@ def main():
         b.record()
         torch.cuda.synchronize()
         ts.append(a.elapsed_time(b))
-    n, m, d, H = N_STATE, N_CTRL, N_STATE + N_CTRL, HIDDEN
+    n, m, d = N_STATE, N_CTRL, N_STATE + N_CTRL
     rows = (T - 1) * B
-    byts, flops = (d + n * d + n) * 4, 2 * H * (d + 2 * n + n * d)
+    byts = (d + n * d + n) * 4
+    if deep:
+        # layer 1; per (layer-2 unit, layer-1 unit) one FMA for z2, one product and d FMAs for the
+        # tangent; per (output, layer-2 unit) the same for the value and the Jacobian
+        H1, H2 = hidden
+        flops = 2 * H1 * d + (H2 * H1 + n * H2) * (2 * d + 3)
+    else:
+        H = hidden[0]
+        flops = 2 * H * (d + 2 * n + n * d)
     t = statistics.median(ts) * 1e-3
     emit(f"# mlp_linearize B={B}: {rows} rows, call (allocation + kernel, device events) median "
          f"{t * 1e3:.3f} ms, min {min(ts):.3f}, max {max(ts):.3f}")
