@@ -22,6 +22,7 @@ MODEL_MLP = 5          # a network, described by an Mlp (one hidden layer, the d
                        # or an Mlp2 (two, dilqr_mlp2_*)
 MLP_SIGMOID, MLP_RELU = 0, 1
 MLP_MAX_HIDDEN = 256   # DILQR_MLP_MAX_HIDDEN
+MLP2_VJP_MAX_HIDDEN1 = 128   # DILQR_MLP2_VJP_MAX_HIDDEN1: the first width the two-layer weight gradient takes
 # (n, m) the one-lane-per-problem kernels are compiled for (csrc/dilqr_common.h DILQR_FOR_EACH_SHAPE)
 LANE_SHAPES = ((3, 1), (5, 1), (4, 3), (4, 1), (2, 1), (4, 2), (6, 2), (6, 1))
 BOUNDS_NONE, BOUNDS_SCALAR, BOUNDS_TENSOR = 0, 1, 2
@@ -114,11 +115,14 @@ SIGNATURES = {
     "dilqr_mlp2_linearize_f32": ([_i, _i, _i, _i, Mlp2, _vp, _vp, _vp, _vp, _vp], _i),
     "dilqr_mlp2_lqr_forward_f32": ([_i, _i, _i, _i, Mlp2, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Bounds, _vp, _f, _i,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "dilqr_mlp2_linearize_vjp_f32": ([_i, _i, _i, _i, Mlp2, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                      _vp, ctypes.c_size_t, _vp], _i),
 }
 # the entry points that return a size, not a status (SIGNATURES is the list of
 # those that return int or a string, which tests/test_abi.py reads off the header)
 SIZE_SIGNATURES = {
     "dilqr_mlp_linearize_vjp_ws_bytes": ([_i, _i, _i, _i, _i, _i], ctypes.c_size_t),
+    "dilqr_mlp2_linearize_vjp_ws_bytes": ([_i, _i, _i, _i, _i, _i, _i], ctypes.c_size_t),
 }
 
 _lib = None

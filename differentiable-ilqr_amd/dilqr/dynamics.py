@@ -14,7 +14,10 @@ of the linearisation (ops.mlp_linearize_diff, generic.DEVICE_MLP_VJP); any
 other NNDynamics keeps the torch graph through grad_input (final_step).  One
 with two hidden layers has a device model too (`device_model(like, deep=True)`,
 csrc/dilqr_mlp2.h), used for the solve when generic.DEVICE_MLP_DEEP is on (it
-ships off); its gradient always goes through the torch graph.
+ships off); its gradient goes through the torch graph unless
+generic.DEVICE_MLP_DEEP_VJP (off too) is on and the first width is within
+N.MLP2_VJP_MAX_HIDDEN1: then it is a HIP backward as well
+(ops.mlp2_linearize_diff, csrc/tu_mlp2_vjp.hip).
 """
 import torch
 import torch.nn.functional as Fn

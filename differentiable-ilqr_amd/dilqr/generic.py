@@ -16,7 +16,8 @@ One Module is not run by torch: an NNDynamics with a device model (one hidden
 layer, sigmoid or relu; NNDynamics.device_model) goes through the HIP MLP
 kernels, the gradient into its weights included — see DEVICE_MLP and
 DEVICE_MLP_VJP below; with DEVICE_MLP_DEEP (off by default) one with two
-hidden layers does too, except for that gradient.
+hidden layers does too, and with DEVICE_MLP_DEEP_VJP (off by default) so does
+that gradient (a first width of at most 128; wider ones keep the torch graph).
 
 lqr_step_forward is the one regular forward of an LQR step: the LQRStep
 factories (lqr_step.py, lqr_step_explicit.py) call it too.  Whether its line
@@ -75,9 +76,17 @@ DEVICE_MLP_VJP = True
 # With DEVICE_MLP, a module with two hidden layers takes the same routes on its
 # own device model (ops.Mlp2Model, csrc/tu_mlp2.hip): rollout, the ANALYTIC
 # linearisation without gradient, the line search and the whole solve.  Its
-# gradient stays on the torch graph through grad_input whatever this says (no
-# device VJP exists for it).  Off: such a module runs in torch, as it always has.
+# gradient stays on the torch graph through grad_input unless
+# DEVICE_MLP_DEEP_VJP says otherwise.  Off: such a module runs in torch, as it
+# always has.
 DEVICE_MLP_DEEP = False
+# With DEVICE_MLP, DEVICE_MLP_DEEP and DEVICE_MLP_VJP, the differentiable
+# ANALYTIC linearisation of final_step for a two-hidden-layer module inside the
+# device VJP's envelope (ops.Mlp2Model.vjp_ok: a first width of at most
+# N.MLP2_VJP_MAX_HIDDEN1) is the Mlp2 kernel with a HIP backward into the six
+# parameters (ops.mlp2_linearize_diff, csrc/tu_mlp2_vjp.hip).  Off, or outside
+# the envelope: the torch graph through NNDynamics.grad_input.
+DEVICE_MLP_DEEP_VJP = False
 
 
 def device_mlp(dynamics, like):
@@ -184,9 +193,13 @@ def linearize(mpc, x, u, dynamics, diff):
         mlp = device_mlp(dynamics, x)
         if isinstance(mlp, ops.MlpModel):
             # the same kernel, with the device VJP into the module's own parameters as its backward
-            # (one hidden layer only: a two-layer model differentiates through grad_input below)
             fc1, fc2 = dynamics.fcs
             return ops.mlp_linearize_diff(mlp, (fc1.weight, fc1.bias, fc2.weight, fc2.bias), x.detach(), u.detach())
+        if DEVICE_MLP_DEEP_VJP and isinstance(mlp, ops.Mlp2Model) and mlp.vjp_ok:
+            # two hidden layers: its own kernel and VJP (any other two-layer model differentiates
+            # through grad_input below)
+            params = tuple(p for fc in dynamics.fcs for p in (fc.weight, fc.bias))
+            return ops.mlp2_linearize_diff(mlp, params, x.detach(), u.detach())
     xs = x[:-1].detach().reshape(-1, n)
     us = u[:-1].detach().reshape(-1, m)
     if gm == GradMethods.ANALYTIC:

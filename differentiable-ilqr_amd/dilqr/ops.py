@@ -61,8 +61,9 @@ class Mlp2Model:
     (csrc/dilqr_mlp2.h): the dilqr_mlp2 descriptor over the module's own
     parameter storage, plus (n, m) and the tensors that keep the pointers
     alive.  Built by NNDynamics.device_model(like, deep=True); stands wherever
-    an MlpModel does, except the weight gradient (mlp_linearize_vjp), which
-    exists for one hidden layer only."""
+    an MlpModel does.  Its weight gradient has its own call (mlp2_linearize_vjp,
+    csrc/tu_mlp2_vjp.hip; mlp_linearize_vjp stays the one-hidden-layer one) and
+    exists when vjp_ok: a first width of at most N.MLP2_VJP_MAX_HIDDEN1."""
     model_id = N.MODEL_MLP
     entry = "dilqr_mlp2_"
 
@@ -78,6 +79,7 @@ class Mlp2Model:
                 raise ValueError("dilqr: MLP weights must be fp32, contiguous, 16-byte aligned, on one device")
         self.n, self.m, self.H1, self.H2, self.device = n, m, H1, H2, W1.device
         self.desc = N.Mlp2(H1, H2, int(activation), int(bool(passthrough)), *(t.data_ptr() for t in self.tensors))
+        self.vjp_ok = H1 <= N.MLP2_VJP_MAX_HIDDEN1     # inside the envelope of dilqr_mlp2_linearize_vjp_f32
 
     check = MlpModel.check
 
@@ -159,6 +161,19 @@ class Dynamics:
         N.call("dilqr_mlp_linearize_vjp_f32", self.n, self.m, T, B, self.mlp.desc, N.ptr(x), N.ptr(u), N.ptr(gF),
                N.ptr(gf), N.ptr(dW1), N.ptr(db1), N.ptr(dW2), N.ptr(db2), int(max_waves), N.ptr(ws), nbytes,
                N.stream(x.device))
+
+    def linearize_vjp2(self, x, u, gF, gf, dW1, db1, dW2, db2, dW3, db3, max_waves=0):
+        """linearize_vjp for the two-hidden-layer model (an Mlp2Model with
+        vjp_ok): the six gradients written into dW1 [H1,n+m], db1 [H1],
+        dW2 [H2,H1], db2 [H2], dW3 [n,H2], db3 [n]; the workspace is allocated
+        here."""
+        T, B = x.shape[:2]
+        nbytes = N.lib().dilqr_mlp2_linearize_vjp_ws_bytes(self.n, self.m, T, B, self.mlp.H1, self.mlp.H2,
+                                                           int(max_waves))
+        ws = torch.empty(max(nbytes // 4, 1), device=x.device)
+        N.call("dilqr_mlp2_linearize_vjp_f32", self.n, self.m, T, B, self.mlp.desc, N.ptr(x), N.ptr(u), N.ptr(gF),
+               N.ptr(gf), N.ptr(dW1), N.ptr(db1), N.ptr(dW2), N.ptr(db2), N.ptr(dW3), N.ptr(db3), int(max_waves),
+               N.ptr(ws), nbytes, N.stream(x.device))
 
     def line_search(self, x_init, C, c, x, u, K, k, bounds, zI, decay, max_ls, x_out, u_out, cost, du_sq, alpha,
                     old_cost=None):
@@ -332,6 +347,81 @@ def mlp_linearize_diff(mlp, params, x, u):
                                for p, t in zip(params, mlp.tensors)):
         raise ValueError("dilqr: mlp_linearize_diff takes the four parameters (W1, b1, W2, b2) the MlpModel reads")
     return _MlpLinearizeDiff.apply(mlp, x.detach(), u.detach(), *params)
+
+
+def mlp2_linearize_vjp(mlp2, x, u, gF, gf, max_waves=0):
+    """mlp_linearize_vjp for the two-hidden-layer Mlp2Model: (dW1 [H1,n+m],
+    db1 [H1], dW2 [H2,H1], db2 [H2], dW3 [n,H2], db3 [n]) for gradients
+    gF [T-1,B,n,n+m] on F and gf [T-1,B,n] on f (None = zeros) at x [T,B,n],
+    u [T,B,m]; three launches, no atomics, the same bits on every run
+    (csrc/tu_mlp2_vjp.hip).  max_waves caps the groups of waves the rows are
+    dealt to (0: the library's defaults); zeros, and nothing launched, at T = 1
+    or B = 0.  The model must be vjp_ok (H1 <= N.MLP2_VJP_MAX_HIDDEN1)."""
+    if not isinstance(mlp2, Mlp2Model):
+        raise TypeError("dilqr: mlp2_linearize_vjp is built for the two-hidden-layer Mlp2Model only")
+    if not mlp2.vjp_ok:
+        raise ValueError(f"dilqr: mlp2_linearize_vjp takes H1 <= {N.MLP2_VJP_MAX_HIDDEN1}; got {mlp2.H1}")
+    x, u = _al16(_f32(x)), _al16(_f32(u))
+    if x.ndimension() != 3 or u.ndimension() != 3:
+        raise ValueError(f"dilqr: mlp2_linearize_vjp takes x [T,B,n], u [T,B,m]; got {tuple(x.shape)}, {tuple(u.shape)}")
+    mlp2.check(x, u)
+    if max_waves < 0:
+        raise ValueError("dilqr: max_waves must be >= 0")
+    T, B = x.shape[:2]
+    n, d = mlp2.n, mlp2.n + mlp2.m
+    gF, gf = (None if g is None else _al16(_f32(g)) for g in (gF, gf))
+    for g, shape, name in ((gF, (max(T - 1, 0), B, n, d), "gF"), (gf, (max(T - 1, 0), B, n), "gf")):
+        if g is None:
+            continue
+        if tuple(g.shape) != shape:
+            raise ValueError(f"dilqr: {name} must be {shape}; got {tuple(g.shape)}")
+        if g.device != mlp2.device:
+            raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
+    rows = max(T - 1, 0) * B
+    new = torch.zeros if rows == 0 else torch.empty
+    out = tuple(new(*t.shape, device=x.device) for t in mlp2.tensors)
+    if rows:
+        Dynamics(mlp2, mlp2.n, mlp2.m).linearize_vjp2(x, u, gF, gf, *out, max_waves=max_waves)
+    return out
+
+
+class _Mlp2LinearizeDiff(torch.autograd.Function):
+    """mlp_linearize on an Mlp2Model with the gradient into its six parameters
+    (W1, b1, W2, b2, W3, b3: the storage the model points at): the
+    linearisation kernel forward, mlp2_linearize_vjp backward.  x and u get no
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, mlp2, x, u, *params):
+        ctx.mlp = mlp2
+        ctx.set_materialize_grads(False)
+        # saved so that an in-place update of a parameter between forward and
+        # backward is refused by autograd (the kernels read the live storage)
+        ctx.save_for_backward(x, u, *params)
+        F, f = mlp_linearize(mlp2, x, u)
+        return F, f
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gF, gf):
+        x, u = ctx.saved_tensors[:2]
+        grads = mlp2_linearize_vjp(ctx.mlp, x, u, gF, gf)
+        return (None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
+
+
+def mlp2_linearize_diff(mlp2, params, x, u):
+    """mlp_linearize(mlp2, x, u) whose F, f carry the gradient into params =
+    (W1, b1, W2, b2, W3, b3), the Parameters the Mlp2Model was made from
+    (NNDynamics.fcs); the same bits as mlp_linearize.  Not differentiable
+    twice, and not with respect to x and u."""
+    params = tuple(params)
+    if not isinstance(mlp2, Mlp2Model) or not mlp2.vjp_ok:
+        raise ValueError("dilqr: mlp2_linearize_diff takes an Mlp2Model inside the weight gradient's envelope (vjp_ok)")
+    if len(params) != 6 or any(p.data_ptr() != t.data_ptr() or p.shape != t.shape
+                               for p, t in zip(params, mlp2.tensors)):
+        raise ValueError("dilqr: mlp2_linearize_diff takes the six parameters (W1, b1, W2, b2, W3, b3) the "
+                         "Mlp2Model reads")
+    return _Mlp2LinearizeDiff.apply(mlp2, x.detach(), u.detach(), *params)
 
 
 def rollout(model_id, theta, x_init, u, F=None, f=None):

@@ -518,7 +518,8 @@ int dilqr_mlp_linearize_vjp_f32(int n, int m, int T, int B, dilqr_mlp mlp, const
    and return the same errors, all before any launch: DILQR_E_ARG for a null or
    misaligned pointer or a bad size, DILQR_E_SHAPE for an unsupported (n, m) or
    a width outside [1, DILQR_MLP_MAX_HIDDEN], DILQR_E_MODE for an unknown
-   activation.  There is no weight-gradient entry point for this model. */
+   activation.  The weight gradient of the linearisation is
+   dilqr_mlp2_linearize_vjp_f32 below. */
 typedef struct dilqr_mlp2 {
   int n_hidden1;                 /* H1                                            */
   int n_hidden2;                 /* H2                                            */
@@ -547,6 +548,53 @@ int dilqr_mlp2_lqr_forward_f32(int n, int m, int T, int B, dilqr_mlp2 mlp, const
                                float linesearch_decay, int max_linesearch_iter,
                                float* x_out, float* u_out, float* cost, float* du_sq,
                                float* alpha, const float* old_cost, void* stream);
+
+/* ---- gradient of the two-layer linearisation into the weights --------------- */
+/* The backward of dilqr_mlp2_linearize_f32 with respect to W1, b1, W2, b2, W3,
+   b3: the vector-Jacobian product of MPC.linearize_dynamics ANALYTIC,
+   mpc.py:494-519 (F = [R S] from NNDynamics.grad_input, dynamics.py:92-130,
+   f = x' - F tau), for incoming gradients gF on F and gf on f.  With tau =
+   [x;u], o = gf, Gb = gF - gf tau^T, a = act(z), g = act'(z) formed from a as
+   above, h = g (1 - 2a) for sigmoid and 0 for relu (the reference's relu mask
+   carries no gradient), z1 = W1 tau + b1, z2 = W2 a1 + b2, per row:
+     P_lk = sum_j W2_lj g1_j W1_jk,     U_lk = sum_i W3_il Gb_ik,
+     p2_l = sum_i W3_il o_i,            s2_l = sum_k U_lk P_lk,
+     zh2_l = g2_l p2_l + h2_l s2_l,     dP_lk = g2_l U_lk,
+     da1_j = sum_l W2_lj zh2_l,         dg1_j = sum_l W2_lj sum_k dP_lk W1_jk,
+     zh1_j = g1_j da1_j + h1_j dg1_j,
+   and summed over the (T-1)*B rows:
+     db3_i = sum o_i,     dW3_il = sum [o_i a2_l + g2_l sum_k Gb_ik P_lk],
+     db2_l = sum zh2_l,   dW2_lj = sum [zh2_l a1_j + g1_j sum_k dP_lk W1_jk],
+     db1_j = sum zh1_j,   dW1_jk = sum [zh1_j tau_k + g1_j sum_l W2_lj dP_lk].
+   x, u, gF, gf as for dilqr_mlp_linearize_vjp_f32 (gF or gf NULL = zeros);
+   dW1 [H1,n+m], db1 [H1], dW2 [H2,H1], db2 [H2], dW3 [n,H2], db3 [n] are
+   written, never accumulated into.  n_hidden1 <= DILQR_MLP2_VJP_MAX_HIDDEN1
+   (a wave owns 64 first-layer units in the sums over rows, a wider layer is
+   split over the grid; the bound keeps the launch within 64 KiB of LDS);
+   n_hidden2 <= DILQR_MLP_MAX_HIDDEN.  Three launches: the first sums the rows
+   on chip (one row per lane; 64-row chunks dealt round-robin to G groups of
+   waves, each wave of a group taking LB second-layer units, LB = 4, or 2
+   where n (n+m) > 30) into G slabs of the workspace, the second adds the slabs
+   in a fixed order, the last writes the outputs.  No atomics: the same inputs
+   give the same bits.  The workspace is the caller's, 16-byte aligned, and
+   needs no initialisation; with C = n+m+1 and NB = ceil(H2 / LB),
+   P = n H2 + H2 + H2 C H1 + NB H1 C + n floats per slab,
+   G = max(1, min(ceil(rows / 64), max_waves or min(512, max(1, 2^24 / P)))),
+   dilqr_mlp2_linearize_vjp_ws_bytes = 4 (G + 1) P bytes, and 0 for sizes the
+   call refuses (n_hidden1 above the constant among them).
+   Errors as dilqr_mlp2_linearize_f32, plus DILQR_E_ARG for a null or
+   misaligned output, a null, misaligned or too small workspace, or
+   max_waves < 0, and DILQR_E_SHAPE for n_hidden1 above the constant.  With
+   T = 1 or B = 0 there are no rows: nothing is launched and the outputs are
+   not written (the gradient is zero).  Graph-capturable; no allocation. */
+#define DILQR_MLP2_VJP_MAX_HIDDEN1 128
+size_t dilqr_mlp2_linearize_vjp_ws_bytes(int n, int m, int T, int B, int n_hidden1,
+                                         int n_hidden2, int max_waves);
+int dilqr_mlp2_linearize_vjp_f32(int n, int m, int T, int B, dilqr_mlp2 mlp, const float* x,
+                                 const float* u, const float* gF, const float* gf,
+                                 float* dW1, float* db1, float* dW2, float* db2,
+                                 float* dW3, float* db3, int max_waves, void* ws,
+                                 size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
