@@ -30,13 +30,16 @@ static inline int grid_for(long long n) { return (int)((n + kBlock - 1) / kBlock
 // prologue, after the sweep, after the line search, exit) and s_memrealtime
 // at entry/exit into a buffer of its own that nothing else reads.
 #ifdef DILQR_STAMPS
-constexpr int kStampSlots = 8, kStampWaves = 4096;
+// (slots 8..11: the boundary regions of an iteration — after the sweep's first
+// step, after the line search's first step, at its loop exit, after B's
+// copy-out; the last iteration's values stay)
+constexpr int kStampSlots = 16, kStampWaves = 4096;
 static __device__ unsigned long long g_stamps[kStampWaves * kStampSlots];
 #define DILQR_STAMP(k)                                                                     \
   do {                                                                                     \
     const unsigned w_ = (blockIdx.x * blockDim.x + threadIdx.x) / 64u;                     \
     if ((threadIdx.x & 63u) == 0 && w_ < (unsigned)kStampWaves)                             \
-      g_stamps[w_ * kStampSlots + (k)] = (k) >= 6 ? __builtin_amdgcn_s_memrealtime()       \
+      g_stamps[w_ * kStampSlots + (k)] = ((k) == 6 || (k) == 7) ? __builtin_amdgcn_s_memrealtime() \
                                                   : __builtin_amdgcn_s_memtime();          \
   } while (0)
 #else

@@ -214,6 +214,26 @@ struct CostDiagConst {
   }
 };
 
+// What a lane of a whole-solve kernel keeps in registers from one phase of its
+// solve to the next (begin -> iteration -> sweep -> line search -> the next
+// iteration), instead of storing it and reading it back a few hundred cycles
+// later with nothing else to issue.  Every field is, bit for
+// bit, the value the load it replaces returns: the MPC slots are rollouts the
+// lane wrote itself, and record 0's state is x_init.  The per-launch kernels
+// enter with an empty carry (CARRY = false) and load as before.
+template <class Model>
+struct LaneCarry {
+  static constexpr int n = Model::N, m = Model::M, d = n + m;
+  float x0[n];                  // x_init: record 0's state, which the sweep's last step (t = 0) holds
+  CostDiagConst<d> cc;          // the cost of a problem flagged kCostDiag | kCostTinv (begin's pk_first)
+  // head of the current trajectory, from the sweep's steps t = 1 and t = 0:
+  // what the line search's first step needs (T = 1: record 1 clamps to record 0)
+  float u0[m], x1[n], u1[m];
+  // tail of the current trajectory, record T-1: from begin's rollout, then the
+  // accepted candidate's at the line search's last step; the next sweep starts on it
+  float xl[n], ul[m];
+};
+
 // The box bounds as a compile-time mode (DILQR_BOUNDS_*): scalar bounds are
 // kernel arguments and per-(t,b) bounds are loaded with the step's other data,
 // so no conditional load exists in the step (a conditional load makes the
@@ -247,6 +267,16 @@ struct SweepIn {
                 int B, int b) {
     cs.load(C, c, t, B, b); ld_xu<TL>(x, u, xp, up, t, B, b); bnd.load(bd, t, B, b);
   }
+  // ... with the step's record handed over in registers (LaneCarry)
+  template <class CostT>
+  DEV void load_carried(const CostT& cs, const float (&xr)[n], const float (&ur)[m], const Bounds& bd, int t, int B,
+                        int b) {
+    cs.load(C, c, t, B, b); bnd.load(bd, t, B, b);
+#pragma unroll
+    for (int i = 0; i < n; ++i) x[i] = xr[i];
+#pragma unroll
+    for (int a = 0; a < m; ++a) u[a] = ur[a];
+  }
 };
 
 // Where the fused iteration keeps its gain records (K_t, k_t), written by the
@@ -278,6 +308,16 @@ struct FwdIn {
       ld(xnext, xp + ((size_t)t1 * B + b) * n);
     }
   }
+  // step 0 with the head of the trajectory handed over in registers (LaneCarry):
+  // only the gain record is read back
+  template <class CostT, class Carry>
+  DEV void load_head(const GainRecs& gr, const CostT& cs, const Bounds& bd, const Carry& cy, int T, int B, int b) {
+    SoaRec<GREC>::load(g, gr.p, T, 0, gr.B, gr.b); cs.load(C, c, 0, B, b); bnd.load(bd, 0, B, b);
+#pragma unroll
+    for (int i = 0; i < n; ++i) xnext[i] = cy.x1[i];
+#pragma unroll
+    for (int a = 0; a < m; ++a) { unext[a] = cy.u1[a]; u[a] = cy.u0[a]; }
+  }
 };
 
 // Prefetch distance of the fused sweep, in steps.  At B = 65536 the
@@ -302,6 +342,26 @@ constexpr int kPF = DILQR_PF;
 constexpr int kPFL = DILQR_PF_LS;                   // the line search's prefetch distance
 static_assert(kPFL == 1 || kPFL == 2, "the line search prefetches one or two steps ahead");
 
+// Steps per batch of candidate B's copy-out (line_search): the LDS reads of a
+// batch are issued together, then its stores.  1 is the former loop (every
+// read waited on right before its store); A/B in profiles/r07.
+#ifndef DILQR_COPY_K
+#define DILQR_COPY_K 5
+#endif
+constexpr int kCopyK = DILQR_COPY_K;
+// The whole-solve kernels thread a LaneCarry through their phases (0: A/B
+// builds only — every phase loads as the per-launch kernels do).
+#ifndef DILQR_SOLVE_CARRY
+#define DILQR_SOLVE_CARRY 1
+#endif
+constexpr bool kSolveCarry = DILQR_SOLVE_CARRY;
+// ... and run the waves whose costs are all time-invariant diagonal in a loop
+// of their own (k_mpc_solve_fixed; 0: A/B builds only)
+#ifndef DILQR_SOLVE_WAVE_DC
+#define DILQR_SOLVE_WAVE_DC 1
+#endif
+constexpr bool kSolveWaveDc = DILQR_SOLVE_WAVE_DC;
+
 #ifndef DILQR_PHASE_SKIP
 #define DILQR_PHASE_SKIP 0
 #endif
@@ -315,15 +375,21 @@ static_assert(kPFL == 1 || kPFL == 2, "the line search prefetches one or two ste
 // PAIR: the common MPC case as its own instantiation — exactly one round of two
 // candidates (max_ls == 2) with B's records in the gain slots — so the step
 // loop carries no test of the round, of "is there a B", of "where does B go".
-template <class Model, int BM, int TL, class CostT, bool PAIR = false>
+// CARRY (the whole-solve kernels): x_init and the head of the current
+// trajectory (u_0, x_1, u_1) come from *cy, so the prologue issues no global
+// load, and record T-1 of the accepted candidate goes back into *cy for the
+// next sweep.
+template <class Model, int BM, int TL, class CostT, bool PAIR = false, bool CARRY = false>
 DEV int line_search(int T, int B, int b, const Model md, const float* __restrict__ x_init, const CostT& cs,
                     const float* __restrict__ x, const float* __restrict__ u, const Bounds& bd, float decay,
                     int max_ls, const GainRecs& ws, float* __restrict__ xa_out,
                     float* __restrict__ ua_out, float* __restrict__ xb_out, float* __restrict__ ub_out,
                     float* __restrict__ du_sq, float old_cost, float& cost_out, float& alpha_out,
-                    bool b_in_gains = false) {
+                    bool b_in_gains = false, LaneCarry<Model>* cy = nullptr) {
   constexpr int n = Model::N, m = Model::M, d = n + m;
   constexpr int GREC = m * n + m;                    // gain record: K, k (component-major)
+  static_assert(!CARRY || TL == TRAJ_REC, "the carry hands over whole [x_t; u_t] records");
+  f2 tl[d];                                           // record T-1 of candidates A, B (CARRY)
   // b_in_gains (one round of candidates, gain records in LDS): candidate B's
   // record t overwrites gain record t, consumed by then (m = 1: both are d
   // floats), and only the problems whose B wins copy it to xb_out at the end —
@@ -356,7 +422,12 @@ DEV int line_search(int T, int B, int b, const Model md, const float* __restrict
     f2 xp[n], dp[n];
     {
       float x0[n];
-      ld(x0, x_init + (size_t)b * n);
+      if constexpr (CARRY) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) x0[i] = cy->x0[i];
+      } else {
+        ld(x0, x_init + (size_t)b * n);
+      }
 #pragma unroll
       for (int i = 0; i < n; ++i) { xp[i] = f2{x0[i], x0[i]}; dp[i] = f2{0.f, 0.f}; }
       if constexpr (TL == TRAJ_AOS) {
@@ -368,10 +439,14 @@ DEV int line_search(int T, int B, int b, const Model md, const float* __restrict
     // step s's record holds x_{s+1} of the current trajectory; indices clamp at T-1
     auto cl = [T](int s) { return s < T ? s : T - 1; };
     FwdIn<n, m, GREC, TL, BM> cur, n1, n2;
-    cur.load(ws, u, cs, x, bd, T, 0, cl(1), B, b);
-    if constexpr (TL == TRAJ_REC) {                     // u_0 from record 0
-      float x0r[n];
-      ld_xu<TL>(x0r, cur.u, x, u, 0, B, b);
+    if constexpr (CARRY) {
+      cur.load_head(ws, cs, bd, *cy, T, B, b);
+    } else {
+      cur.load(ws, u, cs, x, bd, T, 0, cl(1), B, b);
+      if constexpr (TL == TRAJ_REC) {                   // u_0 from record 0
+        float x0r[n];
+        ld_xu<TL>(x0r, cur.u, x, u, 0, B, b);
+      }
     }
     if constexpr (kPFL >= 2) {
       if (T > 1) n1.load(ws, u, cs, x, bd, T, 1, cl(2), B, b);
@@ -440,6 +515,10 @@ DEV int line_search(int T, int B, int b, const Model md, const float* __restrict
 #pragma unroll
       for (int a = 0; a < m; ++a) tau[n + a] = nu[a];
       cp += quad_cost<d, CostT::kDiag>(c.C, c.c, tau);
+      if constexpr (CARRY && LAST) {
+#pragma unroll
+        for (int i = 0; i < d; ++i) tl[i] = tau[i];
+      }
       if constexpr (!LAST) {
         f2 xnext[n];
         md.forward(xp, nu, xnext);
@@ -467,26 +546,49 @@ DEV int line_search(int T, int B, int b, const Model md, const float* __restrict
       step(t, std::false_type{}, cur, n1);
       cur = n1;
       if constexpr (kPFL >= 2) n1 = n2;
+#ifdef DILQR_STAMPS
+      if (t == 0) DILQR_STAMP(9);
+#endif
     }
     step(T - 1, std::true_type{}, cur, n1);
+    DILQR_STAMP(10);
     const float cA = cp.x, cB = cp.y;
     if (!(cA > old_cost) || p == max_ls - 1) { cost = cA; alpha = aA; win = 0; break; }
     if (!(cB > old_cost) || p + 1 == max_ls - 1) { cost = cB; alpha = aB; win = 1; break; }
     alpha = aB * decay;                                     // lqr_step_explicit.py:249
   }
+  if constexpr (CARRY) {                                    // the accepted candidate's record T-1
+#pragma unroll
+    for (int i = 0; i < n; ++i) cy->xl[i] = win ? tl[i].y : tl[i].x;
+#pragma unroll
+    for (int a = 0; a < m; ++a) cy->ul[a] = win ? tl[n + a].y : tl[n + a].x;
+  }
   if constexpr (TL == TRAJ_REC) {
     if (b_in_gains && win == 1) {                           // B won: its records from LDS to its slot
-      for (int t = 0; t < T; ++t) {
-        float rb[d], xt[n], ut[m];
-        SoaRec<d>::load(rb, ws.p, T, t, ws.B, ws.b);
+      // kCopyK steps' LDS reads are in flight before the first store: one LDS
+      // latency per kCopyK steps, not one per step (a wave runs this whenever
+      // any of its 64 problems took B — most waves, in the later iterations)
+      auto copy_steps = [&](int t0, auto k_c) {
+        constexpr int K = decltype(k_c)::value;
+        float rb[K][d];
 #pragma unroll
-        for (int i = 0; i < n; ++i) xt[i] = rb[i];
+        for (int k = 0; k < K; ++k) SoaRec<d>::load(rb[k], ws.p, T, t0 + k, ws.B, ws.b);
 #pragma unroll
-        for (int a = 0; a < m; ++a) ut[a] = rb[n + a];
-        st_xu<TL>(xb_out, nullptr, xt, ut, t, B, b);
-      }
+        for (int k = 0; k < K; ++k) {
+          float xt[n], ut[m];
+#pragma unroll
+          for (int i = 0; i < n; ++i) xt[i] = rb[k][i];
+#pragma unroll
+          for (int a = 0; a < m; ++a) ut[a] = rb[k][n + a];
+          st_xu<TL>(xb_out, nullptr, xt, ut, t0 + k, B, b);
+        }
+      };
+      int t = 0;
+      for (; t + kCopyK <= T; t += kCopyK) copy_steps(t, std::integral_constant<int, kCopyK>{});
+      for (; t < T; ++t) copy_steps(t, std::integral_constant<int, 1>{});
     }
   }
+  DILQR_STAMP(11);
   cost_out = cost;
   alpha_out = alpha;
   return win;
@@ -504,14 +606,18 @@ DEV int line_search(int T, int B, int b, const Model md, const float* __restrict
 // PREV: the current trajectory's cost is prev_cost, the cost the previous
 // MPC iteration's line search computed for it (the accepted candidate), so the
 // sweep forms only C tau for c_back and not the stage costs again.
-template <class Model, int BM, int TL, bool ROLLOUT, class CostT, bool PREV = false>
+// CARRY (the whole-solve kernels): the sweep starts on record T-1 held in *cy
+// (no load to wait for before its first step; the prefetches of T-2, T-3 are
+// in flight behind it), leaves the head records (u_0, x_1, u_1) of the
+// trajectory in *cy as it passes them, and the line search takes them from there.
+template <class Model, int BM, int TL, bool ROLLOUT, class CostT, bool PREV = false, bool CARRY = false>
 DEV int ilqr_problem(int T, int B, int b, const Model md, const float* __restrict__ x_init, const CostT& cs,
                      float* __restrict__ pack_out, unsigned char* __restrict__ sym_out, const float* __restrict__ x,
                      const float* __restrict__ u, const Bounds& bd, float decay, int max_ls,
                      const GainRecs& ws, float* __restrict__ xa_out, float* __restrict__ ua_out,
                      float* __restrict__ xb_out, float* __restrict__ ub_out, float* __restrict__ du_sq,
                      float& cost_out, float& alpha_out, bool b_in_gains = false,
-                     float prev_cost = 0.f, unsigned* flags_out = nullptr) {
+                     float prev_cost = 0.f, unsigned* flags_out = nullptr, LaneCarry<Model>* cy = nullptr) {
   constexpr int n = Model::N, m = Model::M, d = n + m;
   constexpr int MODE = BM == DILQR_BOUNDS_NONE ? GAIN_UNC : GAIN_BOX;
   constexpr int GREC = m * n + m;                    // gain record: K, k (component-major)
@@ -530,8 +636,10 @@ DEV int ilqr_problem(int T, int B, int b, const Model md, const float* __restric
     for (int i = 0; i < n; ++i) xn[i] = 0.f;
     // inputs of step t, t-1 (and t-2 at kPF = 2) in flight together
     SweepIn<n, m, TL, BM> cur, n1, n2;
-    cur.load(cs, x, u, bd, T - 1, B, b);
+    if constexpr (CARRY) cur.load_carried(cs, cy->xl, cy->ul, bd, T - 1, B, b);
+    else cur.load(cs, x, u, bd, T - 1, B, b);
     if constexpr (kPF >= 2) n1.load(cs, x, u, bd, T > 1 ? T - 2 : 0, B, b);
+    const int t_head = T > 1 ? 1 : 0;                   // the step whose record the line search reads as "record 1"
     // step T-1 (F = 0, V = 0) is peeled off the loop, so the loop body always
     // computes the Jacobian (no zero-F defaults materialised at every step;
     // -1 us per fused iteration).  (Rotating the prefetch buffers by role
@@ -603,6 +711,16 @@ DEV int ilqr_problem(int T, int B, int b, const Model md, const float* __restric
       if constexpr (!PREV) old_cost += obj;   // summed over t = T-1..0 (the reference's torch sum has its own order)
 #pragma unroll
       for (int i = 0; i < n; ++i) xn[i] = cur.x[i];
+      if constexpr (CARRY) {
+        if (t == t_head) {
+#pragma unroll
+          for (int i = 0; i < n; ++i) cy->x1[i] = cur.x[i];
+#pragma unroll
+          for (int a = 0; a < m; ++a) cy->u1[a] = cur.u[a];
+        }
+#pragma unroll
+        for (int a = 0; a < m; ++a) cy->u0[a] = cur.u[a];   // (the last step's, t = 0, stays)
+      }
     };
     auto sweep_step = [&](int t, auto last_c) {
       if constexpr (kPF >= 2) n2.load(cs, x, u, bd, t > 1 ? t - 2 : 0, B, b);   // prefetch step t-2
@@ -614,6 +732,7 @@ DEV int ilqr_problem(int T, int B, int b, const Model md, const float* __restric
       if constexpr (kPF >= 2) n1 = n2;
     };
     sweep_step(T - 1, std::true_type{});
+    DILQR_STAMP(8);
 // unrolled twice (headline A/B in the no-SLP build, 4 rounds: 1 1.725e9,
 // 2 1.755e9, 3 1.754e9 problem-iterations/s)
 #ifndef DILQR_SWEEP_UNROLL
@@ -621,6 +740,10 @@ DEV int ilqr_problem(int T, int B, int b, const Model md, const float* __restric
 #endif
 #pragma unroll DILQR_SWEEP_UNROLL
     for (int t = T - 2; t >= 0; --t) sweep_step(t, std::false_type{});
+    if constexpr (CARRY) {                              // x_0: record 0's state is x_init, bit for bit
+#pragma unroll
+      for (int i = 0; i < n; ++i) cy->x0[i] = xn[i];
+    }
     if (sym_out) {
       const unsigned char f = sym ? (unsigned char)(kCostSym | (diag && packed_diag_ok<d>() ? kCostDiag : 0) |
                                                     (tinv ? kCostTinv : 0))
@@ -643,19 +766,23 @@ DEV int ilqr_problem(int T, int B, int b, const Model md, const float* __restric
       CostDiagConst<d> cc;
       cc.set(pk_last);
       if (b_in_gains && max_ls == 2)
-        return line_search<Model, BM, TL, CostDiagConst<d>, true>(T, B, b, md, x_init, cc, x, u, bd, decay, max_ls, ws,
-                                                                  xa_out, ua_out, xb_out, ub_out, du_sq, old_cost,
-                                                                  cost_out, alpha_out, b_in_gains);
-      return line_search<Model, BM, TL>(T, B, b, md, x_init, cc, x, u, bd, decay, max_ls, ws, xa_out, ua_out,
-                                         xb_out, ub_out, du_sq, old_cost, cost_out, alpha_out, b_in_gains);
+        return line_search<Model, BM, TL, CostDiagConst<d>, true, CARRY>(T, B, b, md, x_init, cc, x, u, bd, decay,
+                                                                         max_ls, ws, xa_out, ua_out, xb_out, ub_out,
+                                                                         du_sq, old_cost, cost_out, alpha_out,
+                                                                         b_in_gains, cy);
+      return line_search<Model, BM, TL, CostDiagConst<d>, false, CARRY>(T, B, b, md, x_init, cc, x, u, bd, decay,
+                                                                        max_ls, ws, xa_out, ua_out, xb_out, ub_out,
+                                                                        du_sq, old_cost, cost_out, alpha_out,
+                                                                        b_in_gains, cy);
     }
   }
   if (b_in_gains && max_ls == 2)
-    return line_search<Model, BM, TL, CostT, true>(T, B, b, md, x_init, cs, x, u, bd, decay, max_ls, ws, xa_out,
-                                                   ua_out, xb_out, ub_out, du_sq, old_cost, cost_out, alpha_out,
-                                                   b_in_gains);
-  return line_search<Model, BM, TL>(T, B, b, md, x_init, cs, x, u, bd, decay, max_ls, ws, xa_out, ua_out, xb_out,
-                                     ub_out, du_sq, old_cost, cost_out, alpha_out, b_in_gains);
+    return line_search<Model, BM, TL, CostT, true, CARRY>(T, B, b, md, x_init, cs, x, u, bd, decay, max_ls, ws, xa_out,
+                                                          ua_out, xb_out, ub_out, du_sq, old_cost, cost_out,
+                                                          alpha_out, b_in_gains, cy);
+  return line_search<Model, BM, TL, CostT, false, CARRY>(T, B, b, md, x_init, cs, x, u, bd, decay, max_ls, ws, xa_out,
+                                                         ua_out, xb_out, ub_out, du_sq, old_cost, cost_out, alpha_out,
+                                                         b_in_gains, cy);
 }
 
 template <class Model, int BM>
@@ -735,12 +862,13 @@ struct LaneIter {
   int slot;                                                 // the accepted candidate's slot
 };
 
-template <class Model, int BM, bool LG, bool FIRST, bool PREV = true, int GS = kBlock>
+template <class Model, int BM, bool LG, bool FIRST, bool PREV = true, int GS = kBlock, bool CARRY = false,
+          bool ONLY_DC = false>
 DEV LaneIter mpc_iteration_lane(int T, int B, int b, const Model md, const float* __restrict__ x_init,
                                 const float* __restrict__ C, const float* __restrict__ c, const Bounds& bd,
                                 float decay, int max_ls, const MpcState& S, float* __restrict__ du_sq,
                                 float* __restrict__ lds_gains, int cur, int best, unsigned pk, float prev_cost,
-                                unsigned* flags_out = nullptr) {
+                                unsigned* flags_out = nullptr, LaneCarry<Model>* cy = nullptr) {
   constexpr int n = Model::N, m = Model::M;
   const size_t TBd = (size_t)T * B * (n + m);               // one slot: [T,B,d] records
   int sa, sb;
@@ -764,41 +892,47 @@ DEV LaneIter mpc_iteration_lane(int T, int B, int b, const Model md, const float
                                                   xcur, nullptr, bd, decay, max_ls, gr, xsa, nullptr, xsb, nullptr,
                                                   du_sq, cost, alpha, b_lds, 0.f, flags_out);
   } else {
-    if ((pk & (kCostDiag | kCostTinv)) == (kCostDiag | kCostTinv)) {
+    // ONLY_DC: the caller has established (wave-uniformly) that every problem of
+    // this wave is flagged kCostDiag | kCostTinv, so this instantiation holds no
+    // other cost path (and no join with one: a join makes the compiler wait for
+    // whatever any of the paths may have left in flight, trajectory stores included)
+#ifdef DILQR_ONLY_DIAGCONST                // ISA-listing builds only (tools/loop_stats.py)
+    constexpr bool only_dc = true;
+#else
+    constexpr bool only_dc = ONLY_DC;
+#endif
+    if (only_dc || (pk & (kCostDiag | kCostTinv)) == (kCostDiag | kCostTinv)) {
       if constexpr (packed_diag_ok<n + m>()) {
         CostDiagConst<n + m> cc;
-        cc.init(S.Cpk, T, B, b);
-        win = ilqr_problem<Model, BM, TRAJ_REC, true, CostDiagConst<n + m>, PREV>(T, B, b, md, x_init, cc, nullptr, nullptr, xcur, nullptr, bd,
+        if constexpr (CARRY) cc = cy->cc;                   // begin's pk_first: the record init() reads
+        else cc.init(S.Cpk, T, B, b);
+        win = ilqr_problem<Model, BM, TRAJ_REC, true, CostDiagConst<n + m>, PREV, CARRY>(T, B, b, md, x_init, cc, nullptr, nullptr, xcur, nullptr, bd,
                                                       decay, max_ls, gr, xsa, nullptr, xsb, nullptr, du_sq, cost,
-                                                      alpha, b_lds, prev_cost);
+                                                      alpha, b_lds, prev_cost, nullptr, cy);
       } else {
         __builtin_unreachable();
       }
-#ifdef DILQR_ONLY_DIAGCONST                // ISA-listing builds only (tools/loop_stats.py)
-    } else {
+    } else if constexpr (only_dc) {
       __builtin_unreachable();
-    }
-#else
     } else if (pk & kCostDiag) {           // set by iteration 0 only when packed_diag_ok
       if constexpr (packed_diag_ok<n + m>())
-        win = ilqr_problem<Model, BM, TRAJ_REC, true, CostPacked<n + m, true>, PREV>(T, B, b, md, x_init, CostPacked<n + m, true>{S.Cpk, T}, nullptr,
+        win = ilqr_problem<Model, BM, TRAJ_REC, true, CostPacked<n + m, true>, PREV, CARRY>(T, B, b, md, x_init, CostPacked<n + m, true>{S.Cpk, T}, nullptr,
                                                       nullptr, xcur, nullptr, bd, decay, max_ls, gr, xsa, nullptr, xsb,
-                                                      nullptr, du_sq, cost, alpha, b_lds, prev_cost);
+                                                      nullptr, du_sq, cost, alpha, b_lds, prev_cost, nullptr, cy);
       else
         __builtin_unreachable();
     } else if ((pk & (kCostSym | kCostTinv)) == (kCostSym | kCostTinv))
-      win = ilqr_problem<Model, BM, TRAJ_REC, true, CostPacked<n + m, false, true>, PREV>(T, B, b, md, x_init, CostPacked<n + m, false, true>{S.Cpk, T},
+      win = ilqr_problem<Model, BM, TRAJ_REC, true, CostPacked<n + m, false, true>, PREV, CARRY>(T, B, b, md, x_init, CostPacked<n + m, false, true>{S.Cpk, T},
                                                     nullptr, nullptr, xcur, nullptr, bd, decay, max_ls, gr, xsa, nullptr,
-                                                    xsb, nullptr, du_sq, cost, alpha, b_lds, prev_cost);
+                                                    xsb, nullptr, du_sq, cost, alpha, b_lds, prev_cost, nullptr, cy);
     else if (pk & kCostSym)
-      win = ilqr_problem<Model, BM, TRAJ_REC, true, CostPacked<n + m>, PREV>(T, B, b, md, x_init, CostPacked<n + m>{S.Cpk, T}, nullptr, nullptr,
+      win = ilqr_problem<Model, BM, TRAJ_REC, true, CostPacked<n + m>, PREV, CARRY>(T, B, b, md, x_init, CostPacked<n + m>{S.Cpk, T}, nullptr, nullptr,
                                                     xcur, nullptr, bd, decay, max_ls, gr, xsa, nullptr, xsb, nullptr,
-                                                    du_sq, cost, alpha, b_lds, prev_cost);
+                                                    du_sq, cost, alpha, b_lds, prev_cost, nullptr, cy);
     else
-      win = ilqr_problem<Model, BM, TRAJ_REC, true, CostFull<n + m>, PREV>(T, B, b, md, x_init, full, nullptr, nullptr, xcur, nullptr, bd,
+      win = ilqr_problem<Model, BM, TRAJ_REC, true, CostFull<n + m>, PREV, CARRY>(T, B, b, md, x_init, full, nullptr, nullptr, xcur, nullptr, bd,
                                                     decay, max_ls, gr, xsa, nullptr, xsb, nullptr, du_sq, cost,
-                                                    alpha, b_lds, prev_cost);
-#endif
+                                                    alpha, b_lds, prev_cost, nullptr, cy);
   }
   return LaneIter{cost, alpha, win ? sb : sa};
 }
@@ -960,10 +1094,14 @@ constexpr int slot_layout_nm(int n, int m) { return n + m <= 8 ? TRAJ_REC : TRAJ
 // the same single t = T-1 record for a time-invariant cost, same flags) — so
 // the C stream overlaps the light rollout instead of the Riccati sweep, and
 // iteration 0 runs on the packed copy like every later iteration.
-template <class Model, bool ANALYSE = false>
+// CARRY (the whole-solve kernels): record T-1 of the rollout and, from
+// pk_first, the registers of a time-invariant diagonal cost stay in *cy for
+// the iterations that follow.
+template <class Model, bool ANALYSE = false, bool CARRY = false>
 DEV unsigned mpc_begin_lane(int T, int B, int b, const Model& md, const float* __restrict__ x_init,
                             const float* __restrict__ u_init, const MpcState& S,
-                            const float* __restrict__ C = nullptr, const float* __restrict__ c = nullptr) {
+                            const float* __restrict__ C = nullptr, const float* __restrict__ c = nullptr,
+                            LaneCarry<Model>* cy = nullptr) {
   constexpr int n = Model::N, m = Model::M, d = n + m;
   constexpr int PK = packed_cost_floats<d>();
   S.slot[b] = 0; S.slot[B + b] = 0;
@@ -1011,6 +1149,10 @@ DEV unsigned mpc_begin_lane(int T, int B, int b, const Model& md, const float* _
       const int tp = t + PFB < T ? t + PFB : T - 1;
       load_step(s, tp);
       st_xu<TL>(S.Xs, S.Us, xt, ut, t, B, b);
+      if constexpr (CARRY) {
+#pragma unroll
+        for (int a = 0; a < m; ++a) cy->ul[a] = ut[a];      // (step T-1's stays; xt ends as x_{T-1})
+      }
       if (t < T - 1) {
         md.forward(xt, ut, xn);
 #pragma unroll
@@ -1031,6 +1173,11 @@ DEV unsigned mpc_begin_lane(int T, int B, int b, const Model& md, const float* _
         }
       }
     }
+  }
+  if constexpr (CARRY) {
+#pragma unroll
+    for (int i = 0; i < n; ++i) cy->xl[i] = xt[i];
+    if constexpr (ANALYSE && packed_diag_ok<d>()) cy->cc.set(pk_first);   // (used when the flags say diag | tinv)
   }
   if constexpr (ANALYSE) {
     if (tinv) SoaRec<PK>::store(S.Cpk, pk_first, T, T - 1, B, b);   // the one record a time-invariant copy keeps
@@ -1104,26 +1251,50 @@ __global__ void __launch_bounds__(kBlock, DILQR_SOLVE_OCC) k_mpc_solve_fixed(int
   // iteration 0 then reads the cost as every later iteration does (its sweep
   // sums the current trajectory's cost: nothing before it did); without one
   // (pk = 0) iteration 0 reads the caller's C like the per-launch path
-  const unsigned pk = S.Cpk ? mpc_begin_lane<Model, true>(T, B, b, md, x_init, u_init, S, C, c)
-                            : mpc_begin_lane<Model>(T, B, b, md, x_init, u_init, S);
+  // the lane's carry: x_init, the cost registers, and the head and tail records
+  // of its current trajectory stay in registers from here to the last iteration
+  constexpr bool CY = kSolveCarry;
+  LaneCarry<Model> cy;
+  const unsigned pk = S.Cpk ? mpc_begin_lane<Model, true, CY>(T, B, b, md, x_init, u_init, S, C, c, &cy)
+                            : mpc_begin_lane<Model, false, CY>(T, B, b, md, x_init, u_init, S, nullptr, nullptr, &cy);
   DILQR_STAMP(1);
-  LaneIter r = mpc_iteration_lane<Model, BM, LG, false, false, kSolveLpw>(T, B, b, md, x_init, C, c, bd, decay,
-                                                                          max_ls, S, S.du_sq, lds_gains, 0, 0, pk,
-                                                                          0.f);
-  int cur = r.slot, best = r.slot, best_iter = 0;
-  float best_cost = r.cost;
+  LaneIter r{0.f, 0.f, 0};
+  int cur = 0, best = 0, best_iter = 0;
+  float best_cost = 0.f;
   bool take = true;
-  DILQR_STAMP(3);
   const size_t plane = (size_t)T * m * B;                   // one iteration's du rows
-  for (int it = 1; it < iters; ++it) {
-    if (it == iters - 1) DILQR_STAMP(4);
-    r = mpc_iteration_lane<Model, BM, LG, false, true, kSolveLpw>(T, B, b, md, x_init, C, c, bd, decay, max_ls, S,
-                                                                  S.du_sq + it * plane, lds_gains, cur, best, pk,
-                                                                  r.cost);
-    take = mpc_takes_best(false, r.cost, best_cost, best_cost_eps);
-    if (take) { best_cost = r.cost; best = r.slot; best_iter = it; }
-    cur = r.slot;
-  }
+  // the iterations; only_dc: an instantiation that holds the time-invariant
+  // diagonal cost path alone (mpc_iteration_lane ONLY_DC)
+  auto iterate = [&](auto only_dc) {
+    constexpr bool DC = decltype(only_dc)::value;
+    r = mpc_iteration_lane<Model, BM, LG, false, false, kSolveLpw, CY, DC>(T, B, b, md, x_init, C, c, bd, decay,
+                                                                           max_ls, S, S.du_sq, lds_gains, 0, 0, pk,
+                                                                           0.f, nullptr, &cy);
+    cur = best = r.slot;
+    best_cost = r.cost;
+    DILQR_STAMP(3);
+    for (int it = 1; it < iters; ++it) {
+      if (it == iters - 1) DILQR_STAMP(4);
+      r = mpc_iteration_lane<Model, BM, LG, false, true, kSolveLpw, CY, DC>(T, B, b, md, x_init, C, c, bd, decay,
+                                                                            max_ls, S, S.du_sq + it * plane,
+                                                                            lds_gains, cur, best, pk, r.cost,
+                                                                            nullptr, &cy);
+      take = mpc_takes_best(false, r.cost, best_cost, best_cost_eps);
+      if (take) { best_cost = r.cost; best = r.slot; best_iter = it; }
+      cur = r.slot;
+    }
+  };
+  // A wave whose problems all have a time-invariant diagonal cost (the
+  // reference's callers' diag(q), p: the common case) runs its iterations in a
+  // loop of their own.  The test is wave-uniform (a ballot over the wave's
+  // live lanes), so that loop has no join with the other cost paths inside an
+  // iteration; in the shared loop those joins drain the lane's trajectory
+  // stores at the start and at the end of every iteration.
+  bool wave_dc = false;
+  if constexpr (packed_diag_ok<Model::N + m>() && kSolveWaveDc)
+    wave_dc = __ballot((pk & (kCostDiag | kCostTinv)) != (kCostDiag | kCostTinv)) == 0ull;
+  if (wave_dc) iterate(std::true_type{});
+  else iterate(std::false_type{});
   // the state the per-iteration launches leave behind
   S.cost[b] = r.cost;
   S.alpha[b] = r.alpha;
@@ -1175,6 +1346,10 @@ __global__ void __launch_bounds__(kSmallMax) k_mpc_solve_small(int T, int B, con
   LaneIter r{0.f, 0.f, 0};
   int cur = 0, best = 0, imp = 0;
   float best_cost = 0.f;
+  // (every phase enters with an empty LaneCarry here: this kernel sits at the
+  // 512-register limit, and the carry's ~20 longer-lived registers spilled
+  // into its step loops — 240 -> 344 B of scratch for the tensor-bounds LDS
+  // instantiation, 0 -> 20..76 B for the HBM-gains ones)
   if (act) {
     pk = S.Cpk ? mpc_begin_lane<Model, true>(T, B, b, md, x_init, u_init, S, C, c)
                : mpc_begin_lane<Model>(T, B, b, md, x_init, u_init, S);

@@ -10,6 +10,9 @@ old cost), line search, epilogue.  The clock is s_memtime / s_memrealtime
   python tools/phase_stamps.py [iteration]     # on the GPU box
   BOUNDS=100 python tools/phase_stamps.py       # config 4 (box +-100)
   python tools/phase_stamps.py solve           # the whole-solve launch (k_mpc_solve_fixed)
+
+The solve mode also reports the boundary regions of the last iteration (stamps
+8..11: sweep start, line-search start, candidate B's copy-out).
 """
 import ctypes
 import json
@@ -42,6 +45,7 @@ LIM = float(os.environ.get("BOUNDS", "0"))
 nb, _keep = N.make_bounds(-LIM, LIM) if LIM > 0 else N.make_bounds(None, None)
 s = N.stream(dev)
 W = B // 64
+SLOTS = 16                                      # kStampSlots of the diagnostic build
 lib = N.lib()
 lib.dilqr_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
 lib.dilqr_debug_stamps.restype = ctypes.c_int
@@ -53,9 +57,9 @@ if SOLVE:
     for solve in range(4):
         sv.solve_fixed(N.MODEL_CARTPOLE, theta, x0, C, c, nb, 0.5, 2, 1e-4)
         torch.cuda.synchronize()
-        buf = np.zeros(W * 8, dtype=np.uint64)
-        assert lib.dilqr_debug_stamps(buf.ctypes.data, W * 8) == 0
-        rows.append(buf.reshape(W, 8).astype(np.int64))
+        buf = np.zeros(W * SLOTS, dtype=np.uint64)
+        assert lib.dilqr_debug_stamps(buf.ctypes.data, W * SLOTS) == 0
+        rows.append(buf.reshape(W, SLOTS).astype(np.int64))
     out = {"kernel": "k_mpc_solve_fixed", "iterations": ITERS, "waves": W, "bounds": LIM or None}
     r = rows[-1]
     ghz = (r[:, 5] - r[:, 0]) / ((r[:, 7] - r[:, 6]) / 100e6) / 1e9
@@ -66,6 +70,22 @@ if SOLVE:
         out[name + "_cycles"] = {"median": float(np.median(cyc)), "p10": float(np.percentile(cyc, 10)),
                                  "p90": float(np.percentile(cyc, 90)), "max": float(cyc.max())}
         out[name + "_us_median"] = float(np.median(cyc) / (out["clock_ghz_median"] * 1e3))
+    # the boundary regions of the LAST iteration (stamps 8..11), each with the
+    # per-step cost of the loop that follows it taken off: the sweep's start
+    # (iteration entry -> its first step done), the line search's start (sweep
+    # done -> its first step done) and B's copy-out (loop exit -> search done;
+    # in the last iteration nearly every wave has a B-winner)
+    st = np.concatenate(rows[1:]).astype(np.float64)
+    sweep_step = (st[:, 2] - st[:, 8]) / max(T - 1, 1)
+    ls_step = (st[:, 10] - st[:, 9]) / max(T - 1, 1)
+    for name, cyc in (("sweep_start", st[:, 8] - st[:, 4] - sweep_step), ("sweep_step", sweep_step),
+                      ("line_search_start", st[:, 9] - st[:, 2] - ls_step), ("line_search_step", ls_step),
+                      ("copy_out", st[:, 11] - st[:, 10]), ("last_iteration", st[:, 5] - st[:, 4])):
+        out["boundary_" + name + "_cycles"] = {"median": float(np.median(cyc)), "p10": float(np.percentile(cyc, 10)),
+                                               "p90": float(np.percentile(cyc, 90))}
+    out["boundary_share_of_steady_iteration"] = float(
+        sum(out["boundary_" + k + "_cycles"]["median"] for k in ("sweep_start", "line_search_start", "copy_out"))
+        / out["steady_iteration_cycles"]["median"])
     out["kernel_span_us"] = float(np.median([(x[:, 7].max() - x[:, 6].min()) / 100.0 for x in rows[1:]]))
     out["wave_end_spread_us"] = float(np.median([(x[:, 7].max() - x[:, 7].min()) / 100.0 for x in rows[1:]]))
     out["wave_start_spread_us"] = float(np.median([(x[:, 6].max() - x[:, 6].min()) / 100.0 for x in rows[1:]]))
@@ -90,9 +110,9 @@ for solve in range(4):
                i, 1e-4, 0.0, 10 ** 9, sv.state, s)
         if i == STOP_AT:
             torch.cuda.synchronize()
-            buf = np.zeros(W * 8, dtype=np.uint64)
-            assert lib.dilqr_debug_stamps(buf.ctypes.data, W * 8) == 0
-            rows.append(buf.reshape(W, 8).astype(np.int64))
+            buf = np.zeros(W * SLOTS, dtype=np.uint64)
+            assert lib.dilqr_debug_stamps(buf.ctypes.data, W * SLOTS) == 0
+            rows.append(buf.reshape(W, SLOTS).astype(np.int64))
         N.call("dilqr_mpc_stop_rule_f32", T, m, B, i, sv.state, s)
     torch.cuda.synchronize()
 
