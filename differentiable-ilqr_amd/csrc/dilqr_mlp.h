@@ -17,6 +17,8 @@
 // each workgroup stages them once in LDS and every lane reads the same LDS
 // address (a broadcast).
 #pragma once
+#include <type_traits>
+
 #include "dilqr_device.h"
 
 namespace dilqr {
@@ -89,16 +91,31 @@ struct Mlp {
     }
   }
 
-  template <bool FWD, bool JAC>
-  DEV void walk(const float (&x)[N], const float (&u)[M], float (*o)[N], float (*J)[N][D]) const {
-    float tau[D], acc[N], Jr[N][D];
+  // the line search's pair of candidates: each component is the float
+  // activation of that component (__expf + vrcp, the relu gate), so a packed
+  // evaluation rounds like two scalar ones (dilqr_device.h)
+  static DEV void activate(f2 z, f2& a, f2& g) {
+    float a0, g0, a1, g1;
+    activate(z.x, a0, g0);
+    activate(z.y, a1, g1);
+    a = f2{a0, a1};
+    g = f2{g0, g1};
+  }
+
+  // S: float, or f2 for the value of two trajectories at once (FWD only; the
+  // weights are scalars either way, so each component is the float walk)
+  template <bool FWD, bool JAC, class S>
+  DEV void walk(const S (&x)[N], const S (&u)[M], S (*o)[N], float (*J)[N][D]) const {
+    static_assert(!JAC || std::is_same_v<S, float>, "the Jacobian is formed for one trajectory");
+    S tau[D], acc[N];
+    float Jr[N][D];
 #pragma unroll
     for (int i = 0; i < N; ++i) tau[i] = x[i];
 #pragma unroll
     for (int a = 0; a < M; ++a) tau[N + a] = u[a];
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-      acc[i] = FWD ? b2[i] : 0.f;
+      acc[i] = S(FWD ? b2[i] : 0.f);
 #pragma unroll
       for (int k = 0; k < D; ++k) Jr[i][k] = 0.f;
     }
@@ -107,10 +124,10 @@ struct Mlp {
       float w[D];
 #pragma unroll
       for (int k = 0; k < D; ++k) w[k] = W1[j * D + k];
-      float z = b1[j];
+      S z = S(b1[j]);
 #pragma unroll
       for (int k = 0; k < D; ++k) z += w[k] * tau[k];
-      float a, g;
+      S a, g;
       activate(z, a, g);
 #pragma unroll
       for (int i = 0; i < N; ++i) {
@@ -135,16 +152,23 @@ struct Mlp {
     }
   }
 
-  // dynamics.py:66-90
-  DEV void forward(const float (&x)[N], const float (&u)[M], float (&o)[N]) const {
-    walk<true, false>(x, u, &o, nullptr);
+  // what the fused iteration (dilqr_fused.h) asks of a model besides these:
+  // every entry of the Jacobian is a function of (x, u), and none of it can be
+  // read off the rollout's x_{t+1}
+  using FSparsity = DenseF;
+  static constexpr bool kJacFromNext = false;
+
+  // dynamics.py:66-90 (S = f2: the line search's two candidates)
+  template <class S>
+  DEV void forward(const S (&x)[N], const S (&u)[M], S (&o)[N]) const {
+    walk<true, false, S>(x, u, &o, nullptr);
   }
   // dynamics.py:92-130: [R S]
   DEV void jacobian(const float (&x)[N], const float (&u)[M], float (&J)[N][D]) const {
-    walk<false, true>(x, u, nullptr, &J);
+    walk<false, true, float>(x, u, nullptr, &J);
   }
   DEV void forward_jacobian(const float (&x)[N], const float (&u)[M], float (&o)[N], float (&J)[N][D]) const {
-    walk<true, true>(x, u, &o, &J);
+    walk<true, true, float>(x, u, &o, &J);
   }
 };
 

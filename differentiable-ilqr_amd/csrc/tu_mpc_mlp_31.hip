@@ -1,0 +1,6 @@
+// tu_mpc_mlp_31.hip — the fused iteration and the one-launch small-batch solve
+// on the one-hidden-layer network (dilqr_mlp_fused.h) instantiated for
+// (n, m) = (3, 1): sigmoid and relu, the three bounds modes.
+#include "dilqr_mlp_fused.h"
+
+DILQR_MLP_FUSED_UNIT(3, 1)

@@ -25,6 +25,8 @@ MLP_MAX_HIDDEN = 256   # DILQR_MLP_MAX_HIDDEN
 MLP2_VJP_MAX_HIDDEN1 = 128   # DILQR_MLP2_VJP_MAX_HIDDEN1: the first width the two-layer weight gradient takes
 # (n, m) the one-lane-per-problem kernels are compiled for (csrc/dilqr_common.h DILQR_FOR_EACH_SHAPE)
 LANE_SHAPES = ((3, 1), (5, 1), (4, 3), (4, 1), (2, 1), (4, 2), (6, 2), (6, 1))
+# (n, m) dilqr_mlp_mpc_solve_small_f32 is compiled for (csrc/dilqr_mlp_fused.h mlp_small_ok)
+MLP_SMALL_SHAPES = tuple(s for s in LANE_SHAPES if s != (6, 2))
 BOUNDS_NONE, BOUNDS_SCALAR, BOUNDS_TENSOR = 0, 1, 2
 SOLVE_INV, SOLVE_CHOL = 0, 1
 ERRORS = {1: "unsupported shape/model", 2: "invalid argument", 3: "unsupported option combination"}
@@ -107,6 +109,11 @@ SIGNATURES = {
     "dilqr_mlp_linearize_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp, _vp], _i),
     "dilqr_mlp_lqr_forward_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Bounds, _vp, _f, _i, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "dilqr_mlp_ilqr_iterate_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp, _vp, Bounds, _f, _i, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "dilqr_mlp_mpc_solve_small_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp, Bounds, _f, _i, _i, _f, _f, _i,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp], _i),
     "dilqr_mlp_linearize_vjp_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp,
                                      ctypes.c_size_t, _vp], _i),
     "dilqr_mlp2_dynamics_f32": ([_i, _i, _i, Mlp2, _vp, _vp, _vp, _vp], _i),

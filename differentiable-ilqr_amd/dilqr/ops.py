@@ -186,6 +186,17 @@ class Dynamics:
                float(decay), int(max_ls), N.ptr(x_out), N.ptr(u_out), N.ptr(cost), N.ptr(du_sq), N.ptr(alpha),
                N.ptr(old_cost), N.stream(x.device))
 
+    def fused_iterate(self, x_init, C, c, x, u, bounds, decay, max_ls, ws, x_out, u_out, cost, du_sq, alpha,
+                      old_cost=None, ctrl=None):
+        """linearize + lqr_backward + line_search in one launch (a one-hidden-
+        layer MlpModel only: dilqr_mlp_ilqr_iterate_f32), the same bits in
+        x_out, u_out, cost, du_sq, alpha.  ws: T * B * ilqr_ws_floats(n, m)
+        floats; ctrl: the loop's control word (a no-op once it says stopped)."""
+        T, B = x.shape[:2]
+        N.call("dilqr_mlp_ilqr_iterate_f32", self.n, self.m, T, B, self.mlp.desc, N.ptr(x_init), N.ptr(C), N.ptr(c),
+               N.ptr(x), N.ptr(u), bounds, float(decay), int(max_ls), N.ptr(ws), N.ptr(x_out), N.ptr(u_out),
+               N.ptr(cost), N.ptr(du_sq), N.ptr(alpha), N.ptr(old_cost), N.ptr(ctrl), N.stream(x.device))
+
 
 def device_dynamics(dx, like, env=True, mlp=True, deep=False):
     """The Dynamics handle of a dynamics object for tensors like `like`: a LinDx
@@ -607,13 +618,14 @@ def ilqr_ws_floats(n, m):
 class MPCWorkspace:
     """Device buffers of one MPC solve (reused across iterations)."""
 
-    def __init__(self, T, B, n, m, device, packed_cost=True):
+    def __init__(self, T, B, n, m, device, packed_cost=True, fused=False):
+        """fused: ws also holds the fused iteration's second line-search candidate."""
         dev = device
         self.xa = torch.empty(T, B, n, device=dev)
         self.ua = torch.empty(T, B, m, device=dev)
         self.xb = torch.empty(T, B, n, device=dev)
         self.ub = torch.empty(T, B, m, device=dev)
-        self.ws = torch.empty(T * B * grec_floats(n, m), device=dev)
+        self.ws = torch.empty(T * B * (ilqr_ws_floats(n, m) if fused else grec_floats(n, m)), device=dev)
         self.cost = torch.empty(B, device=dev)
         self.alpha = torch.empty(B, device=dev)
         self.du_sq = torch.empty(T, m, B, device=dev)
@@ -802,6 +814,41 @@ POLL_AHEAD = int(os.environ.get("DILQR_POLL_AHEAD", "2"))
 SMALL_BATCH_MAX = 256
 SMALL_BATCH_MODELS = (N.MODEL_PENDULUM, N.MODEL_CARTPOLE, N.MODEL_PENDULUM_COMPLEX)
 
+# mpc_solve_unfused on a one-hidden-layer MlpModel runs the fused iteration
+# (dilqr_mlp_ilqr_iterate_f32 / dilqr_mlp_mpc_solve_small_f32: the same bits as
+# the four launches per iteration).  False: always the four launches (tests and
+# tools/bench_nn_mpc.py run both routes on the same inputs).
+MLP_FUSED = True
+# the largest batch the per-iteration fused kernel is taken at (None: any):
+# the measured rule of DESIGN.md §6b
+MLP_FUSED_MAX_BATCH = None
+# the largest batch the one-launch solve (dilqr_mlp_mpc_solve_small_f32, up to
+# SMALL_BATCH_MAX problems) is taken at.  0: never.  Measured,
+# it does not beat the four launches at B = 32..128 and loses at 256, one
+# workgroup's waves sharing a CU, while the fused iteration per launch wins at
+# every batch; so the route does not take it (tests and tools set this to
+# SMALL_BATCH_MAX to run it)
+MLP_SMALL_MAX_BATCH = 0
+
+
+def mlp_solve_route(dyn, B, lqr_iter, u_zero_I, verbose):
+    """Which launches mpc_solve_unfused runs for a dynamics (a Dynamics handle
+    or a model): "small", the whole stop-rule solve in one launch (B <=
+    min(SMALL_BATCH_MAX, MLP_SMALL_MAX_BATCH), a shape in N.MLP_SMALL_SHAPES); "fused", the fused iteration +
+    dilqr_mpc_update_best_f32 per iteration; "unfused", the four launches per
+    iteration: everything but a one-hidden-layer MlpModel, a control mask,
+    verbose, MLP_FUSED off, a batch above MLP_FUSED_MAX_BATCH."""
+    mlp = dyn.mlp if isinstance(dyn, Dynamics) else dyn
+    if not MLP_FUSED or not isinstance(mlp, MlpModel) or u_zero_I is not None or verbose > 0:
+        return "unfused"
+    if B < 1 or lqr_iter < 1:
+        return "unfused"
+    if B <= min(SMALL_BATCH_MAX, MLP_SMALL_MAX_BATCH) and (mlp.n, mlp.m) in N.MLP_SMALL_SHAPES:
+        return "small"
+    if MLP_FUSED_MAX_BATCH is not None and B > MLP_FUSED_MAX_BATCH:
+        return "unfused"
+    return "fused"
+
 
 def mpc_solve(model_id, theta, x_init, C, c, T, u_init=None, u_lower=None, u_upper=None, lqr_iter=10,
               eps=1e-7, linesearch_decay=0.2, max_linesearch_iter=10, not_improved_lim=5, best_cost_eps=1e-4,
@@ -951,7 +998,12 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
     the reference's pnqp branch ignores the mask) and zeroed in every rollout
     before the clamp (199-200).  An MlpModel or Mlp2Model (NNDynamics.
     device_model) in place of model_id, or MODEL_MLP with it as theta, runs the
-    loop on the network; which of the two it is only the handle knows.
+    loop on the network; which of the two it is only the handle knows.  A
+    one-hidden-layer MlpModel without a mask and with verbose <= 0 takes the
+    route mlp_solve_route names instead of the four launches: the fused
+    iteration (Dynamics.fused_iterate) + the best/stop rule per iteration, or
+    the whole solve in one launch; both fill the same MPCWorkspace fields with
+    the four launches' bits (best_x, best_u, best_cost, best_du, fdn, ctrl).
 
     The host polls the stop flag every `check_every` iterations: up to
     check_every - 1 iterations after the stop rule fired still run their
@@ -971,14 +1023,45 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
                              f"C {tuple(C.shape)}, c {tuple(c.shape)} at T = {T}")
         if x_init.device != dyn.mlp.device:
             raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
-    ws = MPCWorkspace(T, B, n, m, dev)
+    route = mlp_solve_route(dyn, B, lqr_iter, u_zero_I, verbose)
+    ws = MPCWorkspace(T, B, n, m, dev, fused=route != "unfused")
+    s = N.stream(dev)
+    if route == "small":
+        # the whole stop-rule loop in one launch (one workgroup holds the batch)
+        bounds, keep = N.make_bounds(u_lower, u_upper)
+        u0 = None if u_init is None else _al16(expand_u_init(u_init, T, B, m, dev).expand(T, B, m).contiguous())
+        N.call("dilqr_mlp_mpc_solve_small_f32", n, m, T, B, dyn.mlp.desc, N.ptr(x_init), N.ptr(u0), N.ptr(C),
+               N.ptr(c), bounds, float(linesearch_decay), int(max_linesearch_iter), int(lqr_iter),
+               float(best_cost_eps), float(eps), _lim(not_improved_lim), N.ptr(ws.xa), N.ptr(ws.ua), N.ptr(ws.xb),
+               N.ptr(ws.ub), N.ptr(ws.ws), N.ptr(ws.cost), N.ptr(ws.alpha), N.ptr(ws.du_sq), N.ptr(ws.fdn),
+               N.ptr(ws.best_x), N.ptr(ws.best_u), N.ptr(ws.best_cost), N.ptr(ws.best_du), N.ptr(ws.ctrl), s)
+        del keep
+        return ws
     if u_init is None:
         ws.ua.zero_()
     else:
         ws.ua.copy_(expand_u_init(u_init, T, B, m, dev))
-    s = N.stream(dev)
     zI = zero_mask(u_zero_I, T, B, m, dev)
     dyn.rollout(x_init, ws.ua, ws.xa)
+    if route == "fused":
+        # per iteration two library calls on the workspace's own buffers: the
+        # fused iteration and the best-iterate / stop rule (both no-ops once the
+        # rule fired); the flag is polled as below
+        bounds, keep = N.make_bounds(u_lower, u_upper)
+        lim = _lim(not_improved_lim)
+        for i in range(lqr_iter):
+            dyn.fused_iterate(x_init, C, c, ws.xa, ws.ua, bounds, linesearch_decay, max_linesearch_iter, ws.ws,
+                              ws.xb, ws.ub, ws.cost, ws.du_sq, ws.alpha, old_cost=ws.cost if i > 0 else None,
+                              ctrl=ws.ctrl)
+            N.call("dilqr_mpc_update_best_f32", n, m, T, B, int(i == 0), float(best_cost_eps), float(eps), lim,
+                   N.ptr(ws.xb), N.ptr(ws.ub), N.ptr(ws.cost), N.ptr(ws.du_sq), N.ptr(ws.fdn), N.ptr(ws.best_x),
+                   N.ptr(ws.best_u), N.ptr(ws.best_cost), N.ptr(ws.best_du), N.ptr(ws.ctrl), s)
+            ws.xa, ws.xb = ws.xb, ws.xa
+            ws.ua, ws.ub = ws.ub, ws.ua
+            if check_every and (i + 1) % check_every == 0 and i + 1 < lqr_iter and int(ws.ctrl[1].item()):
+                break
+        del keep
+        return ws
     stats = None
     if verbose > 0:                        # the table rows, reduced on the stream (util.print_solve_log)
         stats = torch.zeros(max(lqr_iter, 1), 3, device=dev)

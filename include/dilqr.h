@@ -469,6 +469,47 @@ int dilqr_mlp_lqr_forward_f32(int n, int m, int T, int B, dilqr_mlp mlp, const f
                               float* x_out, float* u_out, float* cost, float* du_sq,
                               float* alpha, const float* old_cost, void* stream);
 
+/* dilqr_ilqr_iterate_f32 with the network as the model: one fused iLQR
+   iteration for any B (the Jacobian formed on the fly, never stored; Riccati
+   sweep + pnqp; the pair line search), the bits of dilqr_mlp_linearize_f32 +
+   dilqr_lqr_backward_f32 + dilqr_mlp_lqr_forward_f32 in x_out, u_out, cost,
+   du_sq [T,m,B] and alpha.  old_cost [B] (nullable): the current trajectory's
+   cost when the caller has it (the previous line search's value), else the
+   sweep sums it; it may alias cost.  ws: T*B*(ceil4(m*n+m+1) + n + m) floats,
+   16-byte aligned (gain records + the second candidate's trajectory).  ctrl
+   (nullable): no-op when ctrl->stopped.  All three bounds modes; no u_zero_I.
+   Errors as dilqr_mlp_lqr_forward_f32, all before any launch. */
+int dilqr_mlp_ilqr_iterate_f32(int n, int m, int T, int B, dilqr_mlp mlp, const float* x_init,
+                               const float* C, const float* c, const float* x,
+                               const float* u, dilqr_bounds bounds, float linesearch_decay,
+                               int max_linesearch_iter, float* ws, float* x_out,
+                               float* u_out, float* cost, float* du_sq, float* alpha,
+                               const float* old_cost, dilqr_mpc_ctrl* ctrl, void* stream);
+
+/* A whole stop-rule MPC solve on the network in ONE launch, B <= 256 and
+   (n, m) not (6, 2), whose iteration leaves the solve's loop no registers
+   (DILQR_E_SHAPE otherwise), on plain buffers: one workgroup rolls u_init [T,B,m]
+   out (NULL = zeros) into (xa, ua), then runs up to `iterations` (>= 1) fused
+   iterations, the trajectory alternating between (xa, ua) and (xb, ub), each
+   followed by what dilqr_mpc_update_best_f32 does: full_du_norm [B] from the
+   quirk rows of du_sq [T,m,B], the best-iterate test and copy into best_x
+   [T,B,n], best_u [T,B,m], best_cost [B], best_du [B], then the counters and
+   the stop rule, after every iteration, the last one included; the loop ends
+   at a stop.  The same bits in the best buffers and full_du_norm, and the same
+   {iter, stopped, n_not_improved} in *ctrl (written whole; it needs no
+   zeroing), as dilqr_mlp_rollout_f32 followed per iteration by
+   dilqr_mlp_ilqr_iterate_f32 and dilqr_mpc_update_best_f32.  ws as for
+   dilqr_mlp_ilqr_iterate_f32; cost, alpha [B] hold the last iteration's. */
+int dilqr_mlp_mpc_solve_small_f32(int n, int m, int T, int B, dilqr_mlp mlp,
+                                  const float* x_init, const float* u_init, const float* C,
+                                  const float* c, dilqr_bounds bounds, float linesearch_decay,
+                                  int max_linesearch_iter, int iterations, float best_cost_eps,
+                                  float eps, int not_improved_lim, float* xa, float* ua,
+                                  float* xb, float* ub, float* ws, float* cost, float* alpha,
+                                  float* du_sq, float* full_du_norm, float* best_x,
+                                  float* best_u, float* best_cost, float* best_du,
+                                  dilqr_mpc_ctrl* ctrl, void* stream);
+
 /* ---- gradient of the linearisation into the network's weights (ABI 11) ----- */
 /* The backward of dilqr_mlp_linearize_f32 with respect to W1, b1, W2, b2: the
    vector-Jacobian product of MPC.linearize_dynamics ANALYTIC, mpc.py:494-519

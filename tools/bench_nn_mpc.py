@@ -4,16 +4,21 @@ kernels against the torch loop, on the same inputs in one process.
 
 Workload: NNDynamics(5, 1, [100], sigmoid), T = 25, lqr_iter = 10 fixed-count
 (eps = 0, not_improved_lim huge), controls in [-1, 1], a dense SPD cost, one
-whole mpc.MPC.forward under no_grad.  Batches 32, 4096, 65536.  The arm with
-generic.DEVICE_MLP = False is the torch loop (the path before the MLP kernels
-existed).  Per batch and arm: warm-up solves, then repeated solves timed with
-device events, the two arms alternating; median, min and max are printed, and
-the costs of the two arms are compared.  Then the linearisation kernel alone
+whole mpc.MPC.forward under no_grad.  Batches 32, 4096, 65536.  Three arms:
+"torch", generic.DEVICE_MLP = False, the torch loop (the path before the MLP
+kernels existed); "device", the four launches per iteration (ops.MLP_FUSED =
+False); "fused", the route ops.mlp_solve_route picks with ops.MLP_FUSED on (the
+fused iteration per launch); and on request "small", that with the one-launch
+solve switched on for the batches one workgroup holds.  Per batch
+and arm: warm-up solves, then repeated solves timed with device events, the
+arms alternating; median, min and max are printed, the costs are compared with
+the first arm's, and the fused route is held against the four launches' median
+and spread (the routing rule of DESIGN.md §6b).  Then the linearisation kernel alone
 at the largest batch, with its bytes and FLOPs per row.  --hidden 64,64 takes a
 network with two hidden layers instead: the device arm then also turns
 generic.DEVICE_MLP_DEEP on (csrc/tu_mlp2.hip), the torch arm is the same loop.
 
-    python tools/bench_nn_mpc.py [--batches 32,4096,65536] [--hidden 64,64] [--out FILE]
+    python tools/bench_nn_mpc.py [--batches 32,4096,65536] [--arms device,fused] [--hidden 64,64] [--out FILE]
 """
 import argparse
 import os
@@ -80,6 +85,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--budget", type=float, default=60.0, help="seconds of timed solves per batch and arm")
     ap.add_argument("--hidden", default=str(HIDDEN), help="hidden widths: one (default) or two, as 64,64")
+    ap.add_argument("--arms", default="torch,device,fused", help="arms to time, the first one the baseline")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     hidden = [int(h) for h in args.hidden.split(",")]
@@ -105,38 +111,67 @@ def main():
 
     for s in lines:
         print(s, flush=True)
-    def arm(flag):
-        # the device arm: the MLP route on, for two hidden layers its deep switch too
+    # the arms: the torch loop (the path before the MLP kernels existed), the
+    # four launches per iteration (ops.MLP_FUSED off: linearise, sweep, line
+    # search, best/stop rule), and the route ops.mlp_solve_route picks with
+    # ops.MLP_FUSED on (the fused iteration per launch; two hidden layers stay
+    # on the four launches)
+    # ("small": the fused arm with the one-launch solve switched on up to ops.SMALL_BATCH_MAX; it
+    # ships off, so "fused" is the fused iteration per launch at every batch)
+    ARMS = {"torch": (False, False), "device": (True, False), "fused": (True, True), "small": (True, True)}
+    small_max = ops.MLP_SMALL_MAX_BATCH
+    arms = [a for a in args.arms.split(",") if a]
+    if not arms or any(a not in ARMS for a in arms):
+        sys.exit("bench_nn_mpc: --arms takes a list of " + ",".join(ARMS))
+
+    def arm(name):
+        flag, fused = ARMS[name]
         generic.DEVICE_MLP = flag
         generic.DEVICE_MLP_DEEP = flag and deep
+        ops.MLP_FUSED = fused
+        ops.MLP_SMALL_MAX_BATCH = ops.SMALL_BATCH_MAX if name == "small" else small_max
 
     for B in [int(b) for b in args.batches.split(",")]:
         x0, C, c = problem(B, dev)
         cost, mpc = QuadCost(C, c), solver(B)
-        times, costs = {True: [], False: []}, {}
-        for flag in (True, False):
-            arm(flag)
-            for _ in range(args.warmup if flag else 1):
+        times, costs = {a: [] for a in arms}, {}
+        for a in arms:
+            arm(a)
+            for _ in range(1 if a == "torch" else args.warmup):
                 timed_solve(mpc, x0, cost, dx)
-        spent = {True: 0.0, False: 0.0}
+        spent = {a: 0.0 for a in arms}
         for r in range(args.repeats):                      # the arms alternate
-            for flag in (True, False):
-                if r >= 3 and spent[flag] > args.budget:
+            for a in arms:
+                if r >= 3 and spent[a] > args.budget:
                     continue
-                arm(flag)
+                arm(a)
                 t0 = time.perf_counter()
                 ms, cs = timed_solve(mpc, x0, cost, dx)
-                spent[flag] += time.perf_counter() - t0
-                times[flag].append(ms)
-                costs[flag] = cs
-        arm(False)
-        generic.DEVICE_MLP = True
-        rel = float(((costs[True] - costs[False]).abs() / costs[False].abs().clamp(min=1.0)).max())
-        med = {f: statistics.median(times[f]) for f in times}
-        for flag, name in ((False, "torch"), (True, "device")):
-            t = times[flag]
-            emit(f"{B:<8d} {name:<7s} {len(t):<3d} {med[flag]:11.3f} {min(t):11.3f} {max(t):11.3f} "
-                 f"{med[False] / med[flag]:9.2f}   {rel:.2e}")
+                spent[a] += time.perf_counter() - t0
+                times[a].append(ms)
+                costs[a] = cs
+        generic.DEVICE_MLP, generic.DEVICE_MLP_DEEP, ops.MLP_FUSED = True, False, True
+        ops.MLP_SMALL_MAX_BATCH = small_max
+        base = arms[0]                                     # speed-up and cost difference against the first arm
+        med = {a: statistics.median(times[a]) for a in arms}
+        for a in arms:
+            t = times[a]
+            rel = float(((costs[a] - costs[base]).abs() / costs[base].abs().clamp(min=1.0)).max())
+            emit(f"{B:<8d} {a:<7s} {len(t):<3d} {med[a]:11.3f} {min(t):11.3f} {max(t):11.3f} "
+                 f"{med[base] / med[a]:9.2f}   {rel:.2e}")
+        for a in ("fused", "small"):
+            if "device" not in arms or a not in arms:
+                continue
+            # the routing rule of DESIGN.md 6b: a route is taken where it is not slower than the
+            # four launches' median by more than that arm's own min-max spread
+            spread = max(times["device"]) - min(times["device"])
+            same = bool(torch.equal(costs[a], costs["device"]))
+            arm(a)
+            route = ops.mlp_solve_route(dx.device_model(x0, deep=deep), B, LQR_ITER, None, -1)
+            arm("fused")
+            emit(f"# B={B}: arm {a} took route {route}, {a} - four-launch medians {med[a] - med['device']:+.3f} ms, "
+                 f"four-launch spread {spread:.3f} ms: {'ok' if med[a] <= med['device'] + spread else 'SLOWER'}; "
+                 f"costs {'equal bits' if same else 'DIFFER'}")
         del x0, C, c, cost
         torch.cuda.empty_cache()
     # the linearisation kernel alone at the largest batch
