@@ -170,6 +170,79 @@ struct Mlp {
   DEV void forward_jacobian(const float (&x)[N], const float (&u)[M], float (&o)[N], float (&J)[N][D]) const {
     walk<true, true, float>(x, u, &o, &J);
   }
+
+  // The Jacobian and, from the same walk, the Lagrangian Hessian of the
+  // dynamics for multipliers lam (the implicit backward, tu_mlp_implicit.hip):
+  //   M = sum_i lam_i d^2 f_i / d tau^2 = W1^T diag(h) W1,
+  //   h_j = (W2^T lam)_j act''(z_j),  act'' = g (1 - 2a) for sigmoid
+  // (the h of tu_mlp_vjp.hip).  relu has act'' = 0: its M is zero and callers
+  // take jacobian() instead; the passthrough adds nothing to M.  z_j, a_j and
+  // the row W1_j are read once per unit.  M is symmetric:
+  //   FULL  Mu gets its D (D + 1) / 2 entries on and above the diagonal, row by
+  //         row ((0,0), (0,1), .., (0,D-1), (1,1), ..)
+  //   else  My = M y as W1^T (h o (W1 y)): M is never formed
+  template <bool FULL>
+  DEV void jacobian_lag(const float (&x)[N], const float (&u)[M], const float (&lam)[N], const float (*y)[D],
+                        float (&J)[N][D], float (*Mu)[D * (D + 1) / 2], float (*My)[D]) const {
+    static_assert(ACT == DILQR_MLP_SIGMOID, "relu: M = 0, use jacobian()");
+    float tau[D], Jr[N][D];
+#pragma unroll
+    for (int i = 0; i < N; ++i) tau[i] = x[i];
+#pragma unroll
+    for (int a = 0; a < M; ++a) tau[N + a] = u[a];
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+      for (int k = 0; k < D; ++k) Jr[i][k] = 0.f;
+    if constexpr (FULL) {
+#pragma unroll
+      for (int e = 0; e < D * (D + 1) / 2; ++e) (*Mu)[e] = 0.f;
+    } else {
+#pragma unroll
+      for (int k = 0; k < D; ++k) (*My)[k] = 0.f;
+    }
+#pragma unroll 4
+    for (int j = 0; j < H; ++j) {
+      float w[D];
+#pragma unroll
+      for (int k = 0; k < D; ++k) w[k] = W1[j * D + k];
+      float z = b1[j];
+#pragma unroll
+      for (int k = 0; k < D; ++k) z += w[k] * tau[k];
+      float a, g;
+      activate(z, a, g);
+      float p = 0.f;
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const float w2 = W2[i * H + j];
+        p += w2 * lam[i];
+        const float s = w2 * g;
+#pragma unroll
+        for (int k = 0; k < D; ++k) Jr[i][k] += s * w[k];
+      }
+      const float h = p * (g * (1.0f - 2.0f * a));
+      if constexpr (FULL) {
+        int e = 0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          const float hk = h * w[k];
+#pragma unroll
+          for (int l = k; l < D; ++l) (*Mu)[e++] += hk * w[l];
+        }
+      } else {
+        float wy = 0.f;
+#pragma unroll
+        for (int k = 0; k < D; ++k) wy += w[k] * (*y)[k];
+        const float hw = h * wy;
+#pragma unroll
+        for (int k = 0; k < D; ++k) (*My)[k] += hw * w[k];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+      for (int k = 0; k < D; ++k) J[i][k] = (pt && i == k) ? Jr[i][k] + 1.0f : Jr[i][k];
+  }
 };
 
 }  // namespace dilqr

@@ -116,6 +116,9 @@ SIGNATURES = {
                                        _vp], _i),
     "dilqr_mlp_linearize_vjp_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp,
                                      ctypes.c_size_t, _vp], _i),
+    "dilqr_mlp_implicit_ws_floats": ([_i, _i], _i),
+    "dilqr_mlp_implicit_backward_f32": ([_i, _i, _i, _i, Mlp, _vp, _vp, _vp, _vp, _vp, _vp, Bounds, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp], _i),
     "dilqr_mlp2_dynamics_f32": ([_i, _i, _i, Mlp2, _vp, _vp, _vp, _vp], _i),
     "dilqr_mlp2_linear_dyn_f32": ([_i, _i, _i, Mlp2, _vp, _vp, _vp, _vp], _i),
     "dilqr_mlp2_rollout_f32": ([_i, _i, _i, _i, Mlp2, _vp, _vp, _vp, _vp], _i),

@@ -17,7 +17,9 @@ csrc/dilqr_mlp2.h), used for the solve when generic.DEVICE_MLP_DEEP is on (it
 ships off); its gradient goes through the torch graph unless
 generic.DEVICE_MLP_DEEP_VJP (off too) is on and the first width is within
 N.MLP2_VJP_MAX_HIDDEN1: then it is a HIP backward as well
-(ops.mlp2_linearize_diff, csrc/tu_mlp2_vjp.hip).
+(ops.mlp2_linearize_diff, csrc/tu_mlp2_vjp.hip).  Through mpc_explicit.MPC a
+one-hidden-layer module gets the DiLQR implicit backward on its device model
+(ops.mlp_implicit_step, csrc/tu_mlp_implicit.hip, generic.DEVICE_MLP_IMPLICIT).
 """
 import torch
 import torch.nn.functional as Fn

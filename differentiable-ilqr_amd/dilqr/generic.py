@@ -87,6 +87,14 @@ DEVICE_MLP_DEEP = False
 # parameters (ops.mlp2_linearize_diff, csrc/tu_mlp2_vjp.hip).  Off, or outside
 # the envelope: the torch graph through NNDynamics.grad_input.
 DEVICE_MLP_DEEP_VJP = False
+# With DEVICE_MLP, the DiLQR implicit backward of final_step (mpc_explicit.MPC)
+# for a one-hidden-layer module, a quadratic cost, the ANALYTIC linearisation,
+# no slew-rate penalty, delta_u or u_zero_I is a HIP kernel on the device model
+# (ops.mlp_implicit_step, csrc/tu_mlp_implicit.hip): the derivative of the iLQR
+# fixed point with the network's curvature; its dF, df reach the weights through
+# the linearisation's backward (DEVICE_MLP_VJP, or the torch graph).  Off, or
+# outside that envelope: the refusal final_step has always given.
+DEVICE_MLP_IMPLICIT = True
 
 
 def device_mlp(dynamics, like):
@@ -106,6 +114,23 @@ def device_solve_ok(mpc, cost, dx, x_init):
             and mpc.slew_rate_penalty is None and mpc.delta_u is None and getattr(mpc, "verbose", 0) <= 0):
         return None
     return device_mlp(dx, x_init)
+
+
+def implicit_mlp_ok(mpc, cost, dx, x_init):
+    """The MlpModel when final_step's DiLQR implicit backward can run on device
+    (ops.mlp_implicit_step): DEVICE_MLP_IMPLICIT, a one-hidden-layer device
+    model of the solve's (n, m), a quadratic cost, the ANALYTIC linearisation,
+    no slew-rate penalty, no delta_u, no u_zero_I mask."""
+    from .mpc_explicit import GradMethods
+    if not (DEVICE_MLP_IMPLICIT and isinstance(cost, QuadCost) and mpc.grad_method == GradMethods.ANALYTIC
+            and mpc.slew_rate_penalty is None and mpc.delta_u is None and getattr(mpc, "u_zero_I", None) is None):
+        return None
+    if getattr(dx, "model_id", None) is not None or not hasattr(dx, "grad_input"):
+        return None
+    mlp = device_mlp(dx, x_init)
+    if not isinstance(mlp, ops.MlpModel) or (mlp.n, mlp.m) != (mpc.n_state, mpc.n_ctrl):
+        return None
+    return mlp
 
 
 # ---------------------------------------------------------------- dynamics / cost wrappers
@@ -508,7 +533,8 @@ def final_step(mpc, x_init, cost, dx, x, u, classic):
     and cost's parameters; for a network with a device model the linearisation
     and its backward are HIP kernels, DEVICE_MLP_VJP), then the no-op step whose
     backward is the classic adjoint kernel (classic=True) or the DiLQR implicit
-    backward."""
+    backward: an env_dx model's, or for a network inside implicit_mlp_ok's
+    envelope the kernel on its device model (DEVICE_MLP_IMPLICIT)."""
     from .lqr_step import LQRStep as ClassicStep
     from .lqr_step_explicit import LQRStep as ExplicitStep
     T, n, m = mpc.T, mpc.n_state, mpc.n_ctrl
@@ -537,6 +563,11 @@ def final_step(mpc, x_init, cost, dx, x, u, classic):
                            true_dynamics=dx, current_x=x.detach(), current_u=u.detach(), back_eps=mpc.back_eps,
                            no_op_forward=True)
         return step(x_init, C, c, F, f)
+    mlp = implicit_mlp_ok(mpc, cost, dx, x_init)
+    if mlp is not None:
+        # the network: the implicit backward kernel on its device model; dF, df
+        # go on through F, f into the linearisation's backward above
+        return ops.mlp_implicit_step(mlp, x_init, C, c, F, f, x, u, u_lower=mpc.u_lower, u_upper=mpc.u_upper)
     if getattr(dx, "model_id", None) not in (N.MODEL_CARTPOLE, N.MODEL_PENDULUM, N.MODEL_ROCKET):
         # the DiLQR implicit backward needs an env_dx model's second derivatives
         # (the reference reads dx.params and dx.grad_input and raises without

@@ -360,6 +360,97 @@ def mlp_linearize_diff(mlp, params, x, u):
     return _MlpLinearizeDiff.apply(mlp, x.detach(), u.detach(), *params)
 
 
+def mlp_implicit_backward(mlp, dl_dx, dl_du, C, c, x, u, u_lower, u_upper, want_dF=True):
+    """The DiLQR implicit backward at a solution (x [T,B,n], u [T,B,m]) of a
+    solve on the one-hidden-layer MlpModel with cost C [T,B,d,d], c [T,B,d] and
+    box u_lower / u_upper (None, floats or [T,B,m] tensors), for the loss
+    gradients dl_dx, dl_du: the derivative of the iLQR fixed point, curvature of
+    the network included (csrc/tu_mlp_implicit.hip; one launch).  Returns
+    (dx_init [B,n], dC, dc, dF [T-1,B,n,d], df [T-1,B,n]); the gradient into
+    the weights is mlp_linearize_vjp(mlp, x, u, dF, df).  Without want_dF, dF
+    and df are None: not computed, not allocated."""
+    if not isinstance(mlp, MlpModel):
+        raise TypeError("dilqr: mlp_implicit_backward is built for the one-hidden-layer MlpModel only")
+    dl_dx, dl_du, C, c, x, u = (_al16(_f32(t)) for t in (dl_dx, dl_du, C, c, x, u))
+    if x.ndimension() != 3 or u.ndimension() != 3:
+        raise ValueError(f"dilqr: mlp_implicit_backward takes x [T,B,n], u [T,B,m]; got {tuple(x.shape)}, "
+                         f"{tuple(u.shape)}")
+    T, B = x.shape[:2]
+    n, m = mlp.n, mlp.m
+    d = n + m
+    if T < 1 or x.shape[2] != n or tuple(u.shape) != (T, B, m):
+        raise ValueError(f"dilqr: MLP model is (n, m) = {(n, m)}; got x {tuple(x.shape)}, u {tuple(u.shape)}")
+    for t, shape, name in ((dl_dx, (T, B, n), "dl_dx"), (dl_du, (T, B, m), "dl_du"), (C, (T, B, d, d), "C"),
+                           (c, (T, B, d), "c")):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"dilqr: {name} must be {shape}; got {tuple(t.shape)}")
+    if (u_lower is None) != (u_upper is None):
+        raise ValueError("dilqr: u_lower and u_upper go together")
+    for b, name in ((u_lower, "u_lower"), (u_upper, "u_upper")):
+        if isinstance(b, torch.Tensor) and tuple(b.shape) != (T, B, m):
+            raise ValueError(f"dilqr: {name} must be a float or {(T, B, m)}; got {tuple(b.shape)}")
+    for t in (dl_dx, dl_du, C, c, x, u, u_lower, u_upper):
+        if isinstance(t, torch.Tensor) and t.device != mlp.device:
+            raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
+    dev = x.device
+    rec = N.lib().dilqr_mlp_implicit_ws_floats(n, m)
+    if rec < 0:
+        raise ValueError(f"dilqr: no implicit backward kernel for (n, m) = {(n, m)}")
+    bounds, keep = N.make_bounds(u_lower, u_upper)
+    ws = torch.empty(max(T * B * rec, 4), device=dev)
+    dx0 = torch.empty(B, n, device=dev)
+    dC = torch.empty(T, B, d, d, device=dev)
+    dc = torch.empty(T, B, d, device=dev)
+    # at T = 1 there is no F: the kernel is handed no empty outputs
+    want = bool(want_dF) and T > 1
+    dF = torch.empty(T - 1, B, n, d, device=dev) if want else None
+    df = torch.empty(T - 1, B, n, device=dev) if want else None
+    if B > 0:                                       # an empty batch: empty outputs, nothing launched
+        N.call("dilqr_mlp_implicit_backward_f32", n, m, T, B, mlp.desc, N.ptr(C), N.ptr(c), N.ptr(x), N.ptr(u),
+               N.ptr(dl_dx), N.ptr(dl_du), bounds, N.ptr(ws), N.ptr(dx0), N.ptr(dC), N.ptr(dc), N.ptr(dF),
+               N.ptr(df), N.stream(dev))
+    del keep
+    if want_dF and not want:
+        dF, df = torch.zeros(0, B, n, d, device=dev), torch.zeros(0, B, n, device=dev)
+    return dx0, dC, dc, dF, df
+
+
+class _MlpImplicitStep(torch.autograd.Function):
+    """The closing no-op LQR step of a solve on the MlpModel (generic.final_step,
+    classic=False): forward returns the solution, backward is
+    mlp_implicit_backward.  F and f are graph edges only — the kernel
+    linearises at (x, u) itself; their gradients dF, df go on to the
+    linearisation's backward (mlp_linearize_vjp, or the torch graph through
+    grad_input)."""
+
+    @staticmethod
+    def forward(ctx, mlp, lo, hi, x, u, x_init, C, c, F, f):
+        ctx.mlp, ctx.lo, ctx.hi = mlp, lo, hi
+        # the weights are saved so that an in-place update between forward and
+        # backward is refused by autograd (the kernel reads the live storage)
+        ctx.save_for_backward(C, c, x, u, *mlp.tensors)
+        return x.clone(), u.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dl_dx, dl_du):
+        C, c, x, u = ctx.saved_tensors[:4]
+        need = ctx.needs_input_grad
+        dx0, dC, dc, dF, df = mlp_implicit_backward(ctx.mlp, dl_dx, dl_du, C, c, x, u, ctx.lo, ctx.hi,
+                                                    want_dF=need[8] or need[9])
+        grads = (dx0, dC, dc, dF, df)
+        return (None,) * 5 + tuple(g if nd else None for g, nd in zip(grads, need[5:]))
+
+
+def mlp_implicit_step(mlp, x_init, C, c, F, f, x, u, u_lower=None, u_upper=None):
+    """(x, u) carrying the DiLQR implicit gradient into x_init, C, c and,
+    through F and f (the differentiable linearisation at (x, u)), into the
+    network's weights."""
+    lo = u_lower if (u_lower is None or isinstance(u_lower, (int, float))) else u_lower.detach()
+    hi = u_upper if (u_upper is None or isinstance(u_upper, (int, float))) else u_upper.detach()
+    return _MlpImplicitStep.apply(mlp, lo, hi, x.detach(), u.detach(), x_init, C, c, F, f)
+
+
 def mlp2_linearize_vjp(mlp2, x, u, gF, gf, max_waves=0):
     """mlp_linearize_vjp for the two-hidden-layer Mlp2Model: (dW1 [H1,n+m],
     db1 [H1], dW2 [H2,H1], db2 [H2], dW3 [n,H2], db3 [n]) for gradients

@@ -544,6 +544,36 @@ int dilqr_mlp_linearize_vjp_f32(int n, int m, int T, int B, dilqr_mlp mlp, const
                                 float* dW1, float* db1, float* dW2, float* db2,
                                 int max_waves, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- DiLQR implicit backward with the network as the dynamics --------------- */
+/* The derivative of the iLQR fixed point at a solution (x, u) of a solve whose
+   dynamics are the one-hidden-layer network, curvature of the dynamics
+   included.  With tau = [x;u], g = [dl_dx;dl_du], F_t = d mlp / d tau (tau_t),
+   lam_t the primal costates (lqr_step_explicit.py:305-319) and the active set
+   {|u - bound| <= 1e-8} held fixed:
+     M_t = sum_i lam_{t+1,i} d^2 mlp_i / d tau^2 (tau_t) = W1^T diag(h) W1,
+           h_j = (W2^T lam_{t+1})_j act''(z_j), act'' = a(1-a)(1-2a) for sigmoid
+           and 0 for relu; M_{T-1} = 0; the passthrough adds nothing
+     y   = the LQR solution with cost matrices C_t + M_t and linear term -g_t,
+           dynamics F_t from x_0 = 0, active controls zeroed
+     w_t = g_t - M_t y_t,  dlam_t = C_xx y_x + C_xu y_u - w_x + F_x,t^T dlam_{t+1}
+   Outputs: dx_init [B,n] = -dlam_0, dC [T,B,d,d] = -1/2 (y tau^T + tau y^T),
+   dc [T,B,d] = -y, dF [T-1,B,n,d] = -(dlam_{t+1} tau_t^T + lam_{t+1} y_t^T),
+   df [T-1,B,n] = -dlam_{t+1}; dF and df may both be NULL (not computed).  The
+   gradient into the weights is dilqr_mlp_linearize_vjp_f32 applied to (dF, df).
+   The kernel linearises the network at (x, u) itself; no gains are taken.
+   One problem per lane, three passes over T (gains down, y up, gradients
+   down).  ws: T*B*dilqr_mlp_implicit_ws_floats(n, m) floats, 16-byte aligned,
+   no initialisation (-1 for an (n, m) without kernels).  At T = 1: y_x = 0,
+   y_u = C_uu^-1 g_u on the free controls, dF and df are empty and not written.
+   Errors as dilqr_mlp_linearize_f32, all before any launch, plus DILQR_E_ARG
+   for bad bounds or only one of dF, df given; B = 0 launches nothing. */
+int dilqr_mlp_implicit_ws_floats(int n, int m);
+int dilqr_mlp_implicit_backward_f32(int n, int m, int T, int B, dilqr_mlp mlp, const float* C,
+                                    const float* c, const float* x, const float* u,
+                                    const float* dl_dx, const float* dl_du,
+                                    dilqr_bounds bounds, float* ws, float* dx_init, float* dC,
+                                    float* dc, float* dF, float* df, void* stream);
+
 /* ---- learned dynamics: a two-hidden-layer network --------------------------- */
 /* The reference's NNDynamics (dynamics.py:15-130) with len(hidden_sizes) == 2
    (the [H, H] of its IL experiment, il_exp.py:123):

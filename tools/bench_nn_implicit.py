@@ -1,0 +1,186 @@
+#!/usr/bin/env python
+"""Time one training step through learned dynamics (NNDynamics) with the DiLQR
+implicit backward (dilqr.MPC, csrc/tu_mlp_implicit.hip) against the classic
+adjoint (dilqr.mpc.MPC), on the same inputs.
+
+Workload: bench_nn_backward.py's — NNDynamics(5, 1, [100], sigmoid), T = 25,
+lqr_iter = 10 fixed-count, u in [-1, 1], dense SPD cost — one MPC.forward with
+gradients, then (x . wx + u . wu).sum().backward().  Batches 32, 4096, 65536.
+Timed with device events over the whole step (forward and backward); the part
+from the entry of generic.final_step to the end of the backward is reported
+too ("tail": the differentiable linearisation, the no-op step, its backward
+and the weight VJP).
+
+Arms: "implicit" (dilqr.MPC) and "classic" (dilqr.mpc.MPC), alternating run by
+run.  --parent DIR runs the classic arm in a process of its own against the
+package of another checkout (the parent commit, with its own built library):
+the comparison point.  Per batch and arm: one warm-up, then --runs timed runs
+(3); median, min and max.  After each batch ops.mlp_implicit_backward is timed
+by itself, with its bytes and FLOP per (t, b).
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N_STATE, N_CTRL, HIDDEN, T, LQR_ITER = 5, 1, 100, 25, 10
+
+
+def worker(args):
+    sys.path.insert(0, os.path.join(args.pkg, "differentiable-ilqr_amd"))
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("bench_nn_implicit: needs a GPU (no CPU timing)")
+    import dilqr
+    import dilqr.mpc as cmpc
+    from dilqr import QuadCost, generic
+    from dilqr.dynamics import NNDynamics
+    print("DEVICE " + f"{torch.cuda.get_device_name(0)}  torch {torch.__version__}", flush=True)
+    assert os.path.realpath(generic.__file__).startswith(os.path.realpath(args.pkg)), generic.__file__
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    dx = NNDynamics(N_STATE, N_CTRL, hidden_sizes=[HIDDEN], activation="sigmoid").to(dev)
+    params = list(dx.parameters())
+    arms = ["implicit", "classic"] if hasattr(generic, "DEVICE_MLP_IMPLICIT") else ["classic"]
+    mid = {}
+    inner = generic.final_step
+
+    def final_step(*a, **k):
+        mid["ev"] = torch.cuda.Event(enable_timing=True)
+        mid["ev"].record()
+        return inner(*a, **k)
+
+    generic.final_step = final_step
+
+    def run(B, arm, x0, C, c, wx, wu):
+        for p in params:
+            p.grad = None
+        module = dilqr if arm == "implicit" else cmpc
+        mpc = module.MPC(N_STATE, N_CTRL, T, lqr_iter=LQR_ITER, grad_method=module.GradMethods.ANALYTIC, u_lower=-1.0,
+                         u_upper=1.0, n_batch=B, eps=0.0, not_improved_lim=10 ** 9, exit_unconverged=False,
+                         detach_unconverged=False, linesearch_decay=0.2, max_linesearch_iter=10, verbose=-1)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        x, u, _ = mpc(x0, QuadCost(C, c), dx)
+        ((x * wx).sum() + (u * wu).sum()).backward()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b), mid["ev"].elapsed_time(b)
+
+    for B in [int(b) for b in args.batches.split(",")]:
+        g = torch.Generator().manual_seed(1234)                  # bench_nn_mpc.py's problem
+        d = N_STATE + N_CTRL
+        L = torch.randn(T, B, d, d, generator=g)
+        C = (L @ L.transpose(-1, -2) + 0.5 * torch.eye(d)).to(dev)
+        c = torch.randn(T, B, d, generator=g).to(dev)
+        x0 = torch.randn(B, N_STATE, generator=g).to(dev)
+        wx = torch.randn(T, B, N_STATE, generator=g).to(dev)
+        wu = torch.randn(T, B, N_CTRL, generator=g).to(dev)
+        del L
+        step, tail = {a: [] for a in arms}, {a: [] for a in arms}
+        for arm in arms:
+            run(B, arm, x0, C, c, wx, wu)                          # the warm-up
+        for _ in range(args.runs):
+            for arm in arms:
+                s, t = run(B, arm, x0, C, c, wx, wu)
+                step[arm].append(s)
+                tail[arm].append(t)
+        print("RESULT " + json.dumps({"B": B, "step": step, "tail": tail}), flush=True)
+        if "implicit" in arms:
+            kernel_alone(B, dx, dev, x0, C, c, wx, wu)
+        del C, c, x0, wx, wu
+        torch.cuda.empty_cache()
+
+
+def kernel_alone(B, dx, dev, x0, C, c, wx, wu):
+    """ops.mlp_implicit_backward by itself (allocations + the one launch), with and without dF, df."""
+    import torch
+    from dilqr import ops
+    md = dx.device_model(torch.zeros(1, device=dev))
+    n, m, d, H = N_STATE, N_CTRL, N_STATE + N_CTRL, md.H
+    g = torch.Generator().manual_seed(5)
+    u = torch.randn(T, B, m, generator=g).clamp(-1, 1).to(dev)
+    x = ops.mlp_rollout(md, x0, u)
+    G = m * n + m
+    for want in (True, False):
+        for _ in range(3):
+            ops.mlp_implicit_backward(md, wx, wu, C, c, x, u, -1.0, 1.0, want_dF=want)
+        ts = []
+        for _ in range(20):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            ops.mlp_implicit_backward(md, wx, wu, C, c, x, u, -1.0, 1.0, want_dF=want)
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b))
+        # per (t, b), DESIGN.md section 6b: reads C, c twice (passes B, D), x, u three times, dl_dx twice, dl_du
+        # once, the gains and y once each; writes the gains, y, dC, dc (and dF, df).  FLOP: three walks
+        # (B: z 2d, J 2nd + n, p 2n, M d(d+1) + d; C: z 2d, J 2nd + n; D: z 2d, J 2nd + n, p 2n, My 4d + 1; an
+        # activation as 8), the Riccati step (about 2(2 d n^2 + d^2 n) + 4 n^2 m + 2 n m^2) and the outer products
+        byts = 4 * (2 * (d * d + d) + 3 * d + 2 * n + m + 2 * (G + d) + d * d + d + (n * d + n if want else 0))
+        walk = H * ((2 * d + 2 * n * d + n + 8) * 3 + 2 * (2 * n) + d * (d + 1) + d + 4 * d + 1)
+        ricc = 2 * (2 * d * n * n + d * d * n) + 4 * n * n * m + 2 * n * m * m
+        flops = walk + ricc + 3 * d * d + (3 * n * d if want else 0) + 6 * n * d
+        t = statistics.median(ts) * 1e-3
+        print("NOTE " + f"# mlp_implicit_backward B={B} want_dF={want}: call median {t * 1e3:.3f} ms, min {min(ts):.3f}, "
+              f"max {max(ts):.3f}; per (t, b) {byts} B, {flops} FLOP: {T * B * byts / t / 1e12:.3f} TB/s, "
+              f"{T * B * flops / t / 1e12:.2f} TFLOP/s", flush=True)
+
+
+def spawn(pkg, args):
+    cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--pkg", pkg, "--batches", args.batches,
+           "--runs", str(args.runs)]
+    env = {k: v for k, v in os.environ.items() if k != "DILQR_LIB"}         # each tree loads its own library
+    out = subprocess.run(cmd, capture_output=True, text=True, env=env)
+    if out.returncode != 0:
+        sys.exit(f"bench_nn_implicit: worker on {pkg} failed\n{out.stdout}\n{out.stderr}")
+    device = [line[7:] for line in out.stdout.splitlines() if line.startswith("DEVICE ")][0]
+    notes = [line[5:] for line in out.stdout.splitlines() if line.startswith("NOTE ")]
+    return device, [json.loads(line[7:]) for line in out.stdout.splitlines() if line.startswith("RESULT ")], notes
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="32,4096,65536")
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--parent", default=None, help="a checkout of the parent commit with its library built")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--pkg", default=ROOT, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.worker:
+        return worker(args)
+    # this process never opens the GPU: each tree runs in a child of its own
+    trees = [("tree", ROOT)]
+    if args.parent:
+        trees.insert(0, ("parent", args.parent))
+    rows, notes, device = [], [], ""
+    for name, pkg in trees:
+        device, results, more = spawn(pkg, args)
+        notes += more
+        for r in results:
+            for arm in r["step"]:
+                s, t = r["step"][arm], r["tail"][arm]
+                rows.append(f"{r['B']:<8d} {name:<7s} {arm:<9s} {len(s):<3d} {statistics.median(s):11.3f} {min(s):11.3f} "
+                            f"{max(s):11.3f} {statistics.median(t):11.3f} {min(t):11.3f} {max(t):11.3f}")
+    lines = ["# bench_nn_implicit: one training step, dilqr.MPC (DiLQR implicit backward) against dilqr.mpc.MPC "
+             "(classic adjoint)",
+             f"# NNDynamics({N_STATE},{N_CTRL},[{HIDDEN}],sigmoid) T={T} lqr_iter={LQR_ITER} fixed-count, u in [-1,1], "
+             f"dense SPD cost; MPC.forward with gradients + backward; device events; step = the whole of it, tail = "
+             f"from the entry of final_step; {args.runs} runs per arm, alternating; ms",
+             f"# {device}",
+             "B        tree    arm       n    step_median    step_min    step_max tail_median    tail_min    tail_max"]
+    lines += rows + notes
+    print("\n".join(lines), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
