@@ -1,9 +1,16 @@
-// dilqr_mlp_abi.h — host side of the dilqr_mlp_* entry points, shared by the
-// units that define them (tu_mlp.hip, tu_mlp_vjp.hip): the descriptor's checks,
-// its kernel-argument form and the dispatch on (n, m, activation).
+// dilqr_mlp_abi.h — host side of the dilqr_mlp_* and dilqr_mlp2_* entry points,
+// shared by every unit that defines one (tu_mlp.hip, tu_mlp2.hip, tu_mpc_mlp.hip,
+// tu_mlp_implicit.hip, tu_mlp_vjp.hip, tu_mlp2_vjp.hip).  A kind of network is
+// described once, by a traits type (OneHidden, TwoHidden): its C descriptor, its
+// kernel-argument form, its device model, the descriptor's checks and the
+// dynamic LDS of a launch.  The dispatch on (n, m, activation) is written once
+// over the traits.  A third kind of network is one more traits type here.
 #pragma once
+#include <initializer_list>
+
 #include "dilqr_common.h"
 #include "dilqr_mlp.h"
+#include "dilqr_mlp2.h"
 
 namespace dilqr {
 namespace {
@@ -20,25 +27,52 @@ inline bool mlp_shape_ok(int n, int m) {
   return false;
 }
 
-// the descriptor's own errors (the header's order: pointers, shape, activation)
-inline int mlp_check(int n, int m, const dilqr_mlp& p) {
-  const void* ps[] = {p.W1, p.b1, p.W2, p.b2};
-  for (const void* q : ps) if (!q || !al16(q)) return DILQR_E_ARG;
-  if (!mlp_shape_ok(n, m) || p.n_hidden < 1 || p.n_hidden > kMlpMaxHidden) return DILQR_E_SHAPE;
-  if (p.activation != DILQR_MLP_SIGMOID && p.activation != DILQR_MLP_RELU) return DILQR_E_MODE;
+// a descriptor's own errors (the header's order: pointers, shape, activation)
+inline int mlp_check_desc(int n, int m, std::initializer_list<const void*> weights, std::initializer_list<int> widths,
+                          int activation) {
+  for (const void* q : weights) if (!q || !al16(q)) return DILQR_E_ARG;
+  if (!mlp_shape_ok(n, m)) return DILQR_E_SHAPE;
+  for (int H : widths) if (H < 1 || H > kMlpMaxHidden) return DILQR_E_SHAPE;
+  if (activation != DILQR_MLP_SIGMOID && activation != DILQR_MLP_RELU) return DILQR_E_MODE;
   return 0;
 }
 
-inline MlpArg mka(const dilqr_mlp& p) { return MlpArg{p.n_hidden, p.passthrough, p.W1, p.b1, p.W2, p.b2}; }
+// one hidden layer: dilqr_mlp, the model of dilqr_mlp.h
+struct OneHidden {
+  using Desc = dilqr_mlp;
+  using Arg = MlpArg;
+  template <int N_, int M_, int ACT>
+  using Model = Mlp<N_, M_, ACT>;
+  static int check(int n, int m, const Desc& p) {
+    return mlp_check_desc(n, m, {p.W1, p.b1, p.W2, p.b2}, {p.n_hidden}, p.activation);
+  }
+  static Arg arg(const Desc& p) { return Arg{p.n_hidden, p.passthrough, p.W1, p.b1, p.W2, p.b2}; }
+  static size_t lds_bytes(int n, int m, const Arg& a) { return mlp_lds_bytes(n, m, a.H); }
+};
 
-// fn(Tag<Mlp<n, m, activation>>) for a checked descriptor
-template <class Fn>
+// two hidden layers: dilqr_mlp2, the model of dilqr_mlp2.h
+struct TwoHidden {
+  using Desc = dilqr_mlp2;
+  using Arg = Mlp2Arg;
+  template <int N_, int M_, int ACT>
+  using Model = Mlp2<N_, M_, ACT>;
+  static int check(int n, int m, const Desc& p) {
+    return mlp_check_desc(n, m, {p.W1, p.b1, p.W2, p.b2, p.W3, p.b3}, {p.n_hidden1, p.n_hidden2}, p.activation);
+  }
+  static Arg arg(const Desc& p) {
+    return Arg{p.n_hidden1, p.n_hidden2, p.passthrough, p.W1, p.b1, p.W2, p.b2, p.W3, p.b3};
+  }
+  static size_t lds_bytes(int, int, const Arg& a) { return mlp2_lds_bytes(a.H1); }
+};
+
+// fn(Tag<Net::Model<n, m, activation>>) for a checked descriptor
+template <class Net, class Fn>
 int mlp_dispatch(int n, int m, int activation, Fn&& fn) {
-#define X(N_, M_)                                              \
-  if (n == N_ && m == M_) {                                    \
-    if (activation == DILQR_MLP_SIGMOID) fn(Tag<Mlp<N_, M_, DILQR_MLP_SIGMOID>>{}); \
-    else fn(Tag<Mlp<N_, M_, DILQR_MLP_RELU>>{});               \
-    return launched();                                         \
+#define X(N_, M_)                                                                                     \
+  if (n == N_ && m == M_) {                                                                           \
+    if (activation == DILQR_MLP_SIGMOID) fn(Tag<typename Net::template Model<N_, M_, DILQR_MLP_SIGMOID>>{}); \
+    else fn(Tag<typename Net::template Model<N_, M_, DILQR_MLP_RELU>>{});                             \
+    return launched();                                                                                \
   }
   DILQR_FOR_EACH_SHAPE(X)
 #undef X

@@ -70,7 +70,8 @@
 // atomics, counters or fences: the same bits on every run.
 #include "dilqr_common.h"
 #include "dilqr_mlp2.h"
-#include "dilqr_mlp2_abi.h"
+#include "dilqr_mlp_abi.h"
+#include "dilqr_mlp_vjp_common.h"
 
 namespace dilqr {
 
@@ -80,18 +81,10 @@ static_assert(kVjp2MaxHidden1 <= 65535 * kBlock, "one grid z per 64 first-layer 
 static_assert(sizeof(float) * (kVjp2MaxHidden1 * 65 + 3 + 4 * 9 * 64) <= 65536, "a1 and X in 64 KiB of LDS");
 constexpr int kVjp2Stride = 65;                    // odd: see above
 constexpr int kVjp2SlabBudget = 1 << 24;           // floats of slabs under the default cap
-constexpr int kVjp2DefaultGroups = 512;
-constexpr int kVjp2SumSlices = 4;
 
 // layer-2 units per wave: the row (n d + n + d), the walk's z2 / P / dP and the
 // (n + 1 + d + 1) LB + d + 1 + n sums stay in registers
 inline __host__ __device__ constexpr int vjp2_lb(int n, int m) { return n * (n + m) <= 30 ? 4 : 2; }
-
-DEV float wave_sum2(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // the lane's row: tau, o = gf and Gb = gF - gf tau^T; zeros past the last row
 template <class MD>
@@ -359,10 +352,10 @@ __global__ void __launch_bounds__(kBlock) k_mlp2_linearize_vjp(long long rows, M
       if (blockIdx.z == 0) {
 #pragma unroll
         for (int i = 0; i < n; ++i) {
-          const float v = wave_sum2(aW3[q][i]);
+          const float v = wave_sum(aW3[q][i]);
           if (lane == 0) slab[i * H2 + l] = v;
         }
-        const float vb = wave_sum2(ab2[q]);
+        const float vb = wave_sum(ab2[q]);
         if (lane == 0) slab[ob2 + l] = vb;
       }
       if (ju < H1) {
@@ -379,7 +372,7 @@ __global__ void __launch_bounds__(kBlock) k_mlp2_linearize_vjp(long long rows, M
   if (blockIdx.y == 0 && blockIdx.z == 0) {
 #pragma unroll
     for (int i = 0; i < n; ++i) {
-      const float v = wave_sum2(ab3[i]);
+      const float v = wave_sum(ab3[i]);
       if (lane == 0) slab[ob3 + i] = v;
     }
   }
@@ -387,22 +380,22 @@ __global__ void __launch_bounds__(kBlock) k_mlp2_linearize_vjp(long long rows, M
 
 // out[e] = sum_g ws[g][e], e < P: wave s of a workgroup adds slabs s, s + 4, ...
 // in that order, the four sums are added in wave order.  Writes, never accumulates.
-__global__ void __launch_bounds__(kBlock* kVjp2SumSlices) k_mlp2_vjp_sum(int G, int P, const float* __restrict__ ws,
+__global__ void __launch_bounds__(kBlock* kVjpSumSlices) k_mlp2_vjp_sum(int G, int P, const float* __restrict__ ws,
                                                                          float* __restrict__ out) {
-  __shared__ float part[kVjp2SumSlices][kBlock];
+  __shared__ float part[kVjpSumSlices][kBlock];
   const int l = threadIdx.x & (kBlock - 1), s = threadIdx.x / kBlock;
   const int e = blockIdx.x * kBlock + l;
   float acc = 0.f;
   if (e < P) {
 #pragma unroll 4
-    for (int g = s; g < G; g += kVjp2SumSlices) acc += ws[(size_t)g * P + e];
+    for (int g = s; g < G; g += kVjpSumSlices) acc += ws[(size_t)g * P + e];
   }
   part[s][l] = acc;
   __syncthreads();
   if (s != 0 || e >= P) return;
   float v = part[0][l];
 #pragma unroll
-  for (int q = 1; q < kVjp2SumSlices; ++q) v += part[q][l];
+  for (int q = 1; q < kVjpSumSlices; ++q) v += part[q][l];
   out[e] = v;
 }
 
@@ -460,16 +453,6 @@ inline long long vjp2_slab_floats(int n, int m, int H1, int H2) {
   return (long long)n * H2 + H2 + (long long)H2 * C * H1 + (long long)vjp2_blocks(n, m, H2) * H1 * C + n;
 }
 
-// G: one slab per 64-row chunk up to the cap, at least one
-inline long long vjp2_groups(long long rows, int max_waves, long long P) {
-  long long cap = kVjp2SlabBudget / P;
-  cap = cap < 1 ? 1 : cap > kVjp2DefaultGroups ? kVjp2DefaultGroups : cap;
-  if (max_waves > 0) cap = max_waves;
-  const long long chunks = (rows + 63) / 64;
-  const long long g = chunks < cap ? chunks : cap;
-  return g < 1 ? 1 : g;
-}
-
 }  // namespace
 }  // namespace dilqr
 
@@ -483,7 +466,7 @@ size_t dilqr_mlp2_linearize_vjp_ws_bytes(int n, int m, int T, int B, int n_hidde
     return 0;
   const long long rows = (long long)(T - 1) * B;
   const long long P = vjp2_slab_floats(n, m, n_hidden1, n_hidden2);
-  return sizeof(float) * (size_t)((vjp2_groups(rows, max_waves, P) + 1) * P);
+  return sizeof(float) * (size_t)((vjp_groups(rows, max_waves, kVjp2SlabBudget / P) + 1) * P);
 }
 
 int dilqr_mlp2_linearize_vjp_f32(int n, int m, int T, int B, dilqr_mlp2 mlp, const float* x, const float* u,
@@ -493,25 +476,25 @@ int dilqr_mlp2_linearize_vjp_f32(int n, int m, int T, int B, dilqr_mlp2 mlp, con
     return DILQR_E_ARG;
   const void* ps[] = {x, u, gF, gf, dW1, db1, dW2, db2, dW3, db3, ws};
   for (const void* p : ps) if (!al16(p)) return DILQR_E_ARG;
-  if (int rc = mlp2_check(n, m, mlp)) return rc;
+  if (int rc = TwoHidden::check(n, m, mlp)) return rc;
   if (mlp.n_hidden1 > kVjp2MaxHidden1) return DILQR_E_SHAPE;
   if (ws_bytes < dilqr_mlp2_linearize_vjp_ws_bytes(n, m, T, B, mlp.n_hidden1, mlp.n_hidden2, max_waves))
     return DILQR_E_ARG;
   const long long rows = (long long)(T - 1) * B;
   if (rows == 0) return 0;                   // no rows: nothing launched, as every dilqr_mlp2_* call
-  const Mlp2Arg a = mka2(mlp);
+  const Mlp2Arg a = TwoHidden::arg(mlp);
   const int H1 = a.H1, H2 = a.H2, d = n + m;
   const int P = (int)vjp2_slab_floats(n, m, H1, H2);
-  const int G = (int)vjp2_groups(rows, max_waves, P);
+  const int G = (int)vjp_groups(rows, max_waves, kVjp2SlabBudget / P);
   const int NB = vjp2_blocks(n, m, H2);
   float* const w = static_cast<float*>(ws);
   float* const r = w + (size_t)G * P;
   const size_t lds = sizeof(float) * (vjp2_a1_floats(H1) + vjp2_lb(n, m) * (d + 1) * 64);
-  return mlp2_dispatch(n, m, mlp.activation, [&](auto tag) {
+  return mlp_dispatch<TwoHidden>(n, m, mlp.activation, [&](auto tag) {
     using MD = typename decltype(tag)::type;
     k_mlp2_linearize_vjp<MD><<<dim3(G, NB, (H1 + kBlock - 1) / kBlock), kBlock, lds, S(stream)>>>(rows, a, x, u, gF,
                                                                                                  gf, w, P);
-    k_mlp2_vjp_sum<<<(P + kBlock - 1) / kBlock, kBlock * kVjp2SumSlices, 0, S(stream)>>>(G, P, w, r);
+    k_mlp2_vjp_sum<<<(P + kBlock - 1) / kBlock, kBlock * kVjpSumSlices, 0, S(stream)>>>(G, P, w, r);
     const int E = H2 * H1 + H1 * d + H1 + n + n * H2 + H2;
     k_mlp2_vjp_finish<<<(E + kBlock - 1) / kBlock, kBlock, 0, S(stream)>>>(n, d, NB, a, r, dW1, db1, dW2, db2, dW3,
                                                                           db3);

@@ -281,12 +281,12 @@ int dilqr_mlp_implicit_backward_f32(int n, int m, int T, int B, dilqr_mlp mlp, c
   const void* ps[] = {C, c, x, u, dl_dx, dl_du, ws, dx_init, dC, dc, dF, df};
   for (const void* q : ps) if (!al16(q)) return DILQR_E_ARG;
   if (bad_bounds(bounds)) return DILQR_E_ARG;
-  if (int rc = mlp_check(n, m, mlp)) return rc;
+  if (int rc = OneHidden::check(n, m, mlp)) return rc;
   if (B == 0) return 0;
-  const MlpArg a = mka(mlp);
+  const MlpArg a = OneHidden::arg(mlp);
   const Bounds bd = mkb(bounds);
-  const size_t lds = mlp_lds_bytes(n, m, a.H);
-  return mlp_dispatch(n, m, mlp.activation, [&](auto tag) {
+  const size_t lds = OneHidden::lds_bytes(n, m, a);
+  return mlp_dispatch<OneHidden>(n, m, mlp.activation, [&](auto tag) {
     using MD = typename decltype(tag)::type;
     k_mlp_implicit_backward<MD><<<grid_for(B), kBlock, lds, S(stream)>>>(T, B, a, C, c, x, u, dl_dx, dl_du, bd, ws,
                                                                         dx_init, dC, dc, dF, df);

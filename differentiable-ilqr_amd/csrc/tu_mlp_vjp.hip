@@ -29,22 +29,14 @@
 #include "dilqr_common.h"
 #include "dilqr_mlp.h"
 #include "dilqr_mlp_abi.h"
+#include "dilqr_mlp_vjp_common.h"
 
 namespace dilqr {
-
-constexpr int kVjpDefaultGroups = 512;   // cap on G when the caller gives none
-constexpr int kVjpSumSlices = 4;         // kernel B: waves per workgroup, each sums every 4th slab
 
 // hidden units per wave of kernel A: the accumulators ((d + 1 + n) JB) and the
 // row (n d + n + d) stay in registers
 template <class MD>
 constexpr int vjp_block() { return MD::N * MD::D <= 30 ? 8 : 4; }
-
-DEV float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 template <class MD>
 __global__ void __launch_bounds__(kBlock) k_mlp_linearize_vjp(long long rows, MlpArg arg,
@@ -199,13 +191,6 @@ namespace {
 
 inline long long vjp_slab_floats(int n, int m, int H) { return (long long)H * (n + m + 1) + (long long)n * H + n; }
 
-// G: one slab per 64-row chunk up to the cap, at least one
-inline long long vjp_groups(long long rows, int max_waves) {
-  const long long chunks = (rows + 63) / 64, cap = max_waves > 0 ? max_waves : kVjpDefaultGroups;
-  const long long g = chunks < cap ? chunks : cap;
-  return g < 1 ? 1 : g;
-}
-
 }  // namespace
 }  // namespace dilqr
 
@@ -225,17 +210,17 @@ int dilqr_mlp_linearize_vjp_f32(int n, int m, int T, int B, dilqr_mlp mlp, const
   if (T < 1 || B < 0 || max_waves < 0 || !x || !u || !dW1 || !db1 || !dW2 || !db2 || !ws) return DILQR_E_ARG;
   const void* ps[] = {x, u, gF, gf, dW1, db1, dW2, db2, ws};
   for (const void* p : ps) if (!al16(p)) return DILQR_E_ARG;
-  if (int rc = mlp_check(n, m, mlp)) return rc;
+  if (int rc = OneHidden::check(n, m, mlp)) return rc;
   if (ws_bytes < dilqr_mlp_linearize_vjp_ws_bytes(n, m, T, B, mlp.n_hidden, max_waves)) return DILQR_E_ARG;
   const long long rows = (long long)(T - 1) * B;
   if (rows == 0) return 0;                   // no rows: nothing launched, as every dilqr_mlp_* call
-  const MlpArg a = mka(mlp);
+  const MlpArg a = OneHidden::arg(mlp);
   const int H = a.H, d = n + m;
   const int P = (int)vjp_slab_floats(n, m, H);
   const int G = (int)vjp_groups(rows, max_waves);
-  const size_t lds = mlp_lds_bytes(n, m, H);
+  const size_t lds = OneHidden::lds_bytes(n, m, a);
   float* w = static_cast<float*>(ws);
-  return mlp_dispatch(n, m, mlp.activation, [&](auto tag) {
+  return mlp_dispatch<OneHidden>(n, m, mlp.activation, [&](auto tag) {
     using MD = typename decltype(tag)::type;
     constexpr int JB = vjp_block<MD>();
     k_mlp_linearize_vjp<MD><<<dim3(G, (H + JB - 1) / JB), kBlock, lds, S(stream)>>>(rows, a, x, u, gF, gf, w, P);

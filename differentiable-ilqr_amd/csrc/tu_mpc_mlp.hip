@@ -20,9 +20,9 @@ int dilqr_mlp_ilqr_iterate_f32(int n, int m, int T, int B, dilqr_mlp mlp, const 
   const void* ps[] = {x_init, C, c, x, u, ws, x_out, u_out};
   for (const void* p : ps) if (!al16(p)) return DILQR_E_ARG;
   if (bad_bounds(bounds)) return DILQR_E_ARG;
-  if (int rc = mlp_check(n, m, mlp)) return rc;
+  if (int rc = OneHidden::check(n, m, mlp)) return rc;
   if (B == 0) return 0;
-  const MlpIterArgs a{T, B, mka(mlp), x_init, C, c, x, u, mkb(bounds), linesearch_decay, max_linesearch_iter,
+  const MlpIterArgs a{T, B, OneHidden::arg(mlp), x_init, C, c, x, u, mkb(bounds), linesearch_decay, max_linesearch_iter,
                       ws, x_out, u_out, cost, du_sq, alpha, old_cost, ctrl, S(stream)};
 #define X(N_, M_) if (n == N_ && m == M_) return launch_mlp_ilqr_iterate_##N_##_##M_(a, mlp.activation);
   DILQR_FOR_EACH_SHAPE(X)
@@ -44,10 +44,10 @@ int dilqr_mlp_mpc_solve_small_f32(int n, int m, int T, int B, dilqr_mlp mlp, con
   const void* ps[] = {x_init, u_init, C, c, xa, ua, xb, ub, ws, best_x, best_u};
   for (const void* p : ps) if (!al16(p)) return DILQR_E_ARG;
   if (bad_bounds(bounds)) return DILQR_E_ARG;
-  if (int rc = mlp_check(n, m, mlp)) return rc;
+  if (int rc = OneHidden::check(n, m, mlp)) return rc;
   if (B > kSmallMax || !mlp_small_ok(n, m)) return DILQR_E_SHAPE;
   if (B == 0) return 0;
-  const MlpSolveArgs a{T, B, mka(mlp), x_init, u_init, C, c, mkb(bounds), linesearch_decay, max_linesearch_iter,
+  const MlpSolveArgs a{T, B, OneHidden::arg(mlp), x_init, u_init, C, c, mkb(bounds), linesearch_decay, max_linesearch_iter,
                        iterations, best_cost_eps, eps, not_improved_lim,
                        MlpSolveBufs{xa, ua, xb, ub, ws, cost, alpha, du_sq, full_du_norm, best_x, best_u, best_cost,
                                     best_du, ctrl},

@@ -216,15 +216,14 @@ def linearize(mpc, x, u, dynamics, diff):
             return ops.mlp_linearize(mlp, x.detach(), u.detach())
     if gm == GradMethods.ANALYTIC and diff and mid is None and hasattr(dynamics, "grad_input") and DEVICE_MLP_VJP:
         mlp = device_mlp(dynamics, x)
-        if isinstance(mlp, ops.MlpModel):
-            # the same kernel, with the device VJP into the module's own parameters as its backward
-            fc1, fc2 = dynamics.fcs
-            return ops.mlp_linearize_diff(mlp, (fc1.weight, fc1.bias, fc2.weight, fc2.bias), x.detach(), u.detach())
-        if DEVICE_MLP_DEEP_VJP and isinstance(mlp, ops.Mlp2Model) and mlp.vjp_ok:
-            # two hidden layers: its own kernel and VJP (any other two-layer model differentiates
-            # through grad_input below)
+        one = isinstance(mlp, ops.MlpModel)
+        if one or (DEVICE_MLP_DEEP_VJP and isinstance(mlp, ops.Mlp2Model) and mlp.vjp_ok):
+            # the same kernel, with the device VJP of its kind of network into the module's own
+            # parameters as its backward (any other two-layer model differentiates through
+            # grad_input below)
             params = tuple(p for fc in dynamics.fcs for p in (fc.weight, fc.bias))
-            return ops.mlp2_linearize_diff(mlp, params, x.detach(), u.detach())
+            diff_of = ops.mlp_linearize_diff if one else ops.mlp2_linearize_diff
+            return diff_of(mlp, params, x.detach(), u.detach())
     xs = x[:-1].detach().reshape(-1, n)
     us = u[:-1].detach().reshape(-1, m)
     if gm == GradMethods.ANALYTIC:

@@ -8,6 +8,12 @@ device_dynamics from a dynamics object or by Dynamics.of from the public
 functions' (model_id, theta, F, f).  Its three launches (rollout, linearise,
 line search) are the only call sites of those entry points; rollout,
 linearize, mlp_*, lqr_forward and mpc_solve_unfused all go through them.
+
+A network is an MlpModel (one hidden layer) or an Mlp2Model (two).  Both take
+their validation from _NetModel and differ in what a kind declares: the prefix
+of its entry points, its descriptor, its widths.  The public mlp_* / mlp2_*
+pairs (linearize_vjp, linearize_diff) keep their own refusals over one
+implementation (_linearize_vjp, _LinearizeDiff, Dynamics.linearize_vjp).
 """
 import collections
 import os
@@ -25,27 +31,30 @@ def _f32(t):
     return t.detach().contiguous()
 
 
-class MlpModel:
-    """A one-hidden-layer network as the dilqr_mlp_* entry points take it: the
-    dilqr_mlp descriptor (sizes, flags, raw pointers into the module's own
-    parameter storage: nothing is copied) plus (n, m) and the tensors that keep
-    the pointers alive.  Built by NNDynamics.device_model; passed to
-    lqr_forward / mpc_solve_unfused in place of (model_id, theta)."""
+class _NetModel:
+    """What every kind of network model shares: the validation of (n, m), the
+    widths and the weights (W, b per layer in torch's nn.Linear layouts, the
+    expected shapes derived from the widths), the descriptor over the module's
+    own parameter storage (nothing is copied) and the tensors that keep its
+    pointers alive.  A kind gives entry (the prefix of its entry points:
+    entry + "rollout_f32", ...), Desc (its descriptor: the widths, the flags,
+    the pointers) and the two texts its errors quote."""
     model_id = N.MODEL_MLP
-    entry = "dilqr_mlp_"                # its entry points: entry + "rollout_f32", ...
 
-    def __init__(self, n, m, activation, passthrough, W1, b1, W2, b2):
-        H = W1.shape[0]
-        if (n, m) not in N.LANE_SHAPES or not 1 <= H <= N.MLP_MAX_HIDDEN:
-            raise ValueError(f"dilqr: no MLP kernels for (n, m) = {(n, m)}, H = {H}")
-        if (tuple(W1.shape), tuple(b1.shape), tuple(W2.shape), tuple(b2.shape)) != ((H, n + m), (H,), (n, H), (n,)):
-            raise ValueError("dilqr: MLP weights must be W1 [H,n+m], b1 [H], W2 [n,H], b2 [n]")
-        for t in (W1, b1, W2, b2):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != W1.device or t.data_ptr() % 16:
+    def __init__(self, n, m, activation, passthrough, *tensors):
+        widths = tuple(W.shape[0] for W in tensors[:-2:2])
+        if (n, m) not in N.LANE_SHAPES or not all(1 <= H <= N.MLP_MAX_HIDDEN for H in widths):
+            raise ValueError(f"dilqr: no MLP kernels for (n, m) = {(n, m)}, {self.width_names} = "
+                             f"{widths[0] if len(widths) == 1 else widths}")
+        sizes = (n + m,) + widths + (n,)
+        shapes = tuple(s for fan_in, fan_out in zip(sizes, sizes[1:]) for s in ((fan_out, fan_in), (fan_out,)))
+        if tuple(tuple(t.shape) for t in tensors) != shapes:
+            raise ValueError(f"dilqr: MLP weights must be {self.layout}")
+        for t in tensors:
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != tensors[0].device or t.data_ptr() % 16:
                 raise ValueError("dilqr: MLP weights must be fp32, contiguous, 16-byte aligned, on one device")
-        self.n, self.m, self.H, self.device = n, m, H, W1.device
-        self.tensors = (W1, b1, W2, b2)
-        self.desc = N.Mlp(H, int(activation), int(bool(passthrough)), *(t.data_ptr() for t in self.tensors))
+        self.n, self.m, self.widths, self.device, self.tensors = n, m, widths, tensors[0].device, tensors
+        self.desc = self.Desc(*widths, int(activation), int(bool(passthrough)), *(t.data_ptr() for t in tensors))
 
     def check(self, x, u):
         """x [..., n], u [..., m] on the weights' device (the kernels index rows by n and m)."""
@@ -56,32 +65,35 @@ class MlpModel:
             raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
 
 
-class Mlp2Model:
+class MlpModel(_NetModel):
+    """A one-hidden-layer network as the dilqr_mlp_* entry points take it: the
+    dilqr_mlp descriptor plus (n, m), H and the tensors.  Built by
+    NNDynamics.device_model; passed to lqr_forward / mpc_solve_unfused in place
+    of (model_id, theta)."""
+    entry, Desc = "dilqr_mlp_", N.Mlp
+    width_names, layout = "H", "W1 [H,n+m], b1 [H], W2 [n,H], b2 [n]"
+
+    def __init__(self, n, m, activation, passthrough, W1, b1, W2, b2):
+        super().__init__(n, m, activation, passthrough, W1, b1, W2, b2)
+        self.H, = self.widths
+
+
+class Mlp2Model(_NetModel):
     """A two-hidden-layer network as the dilqr_mlp2_* entry points take it
-    (csrc/dilqr_mlp2.h): the dilqr_mlp2 descriptor over the module's own
-    parameter storage, plus (n, m) and the tensors that keep the pointers
-    alive.  Built by NNDynamics.device_model(like, deep=True); stands wherever
-    an MlpModel does.  Its weight gradient has its own call (mlp2_linearize_vjp,
-    csrc/tu_mlp2_vjp.hip; mlp_linearize_vjp stays the one-hidden-layer one) and
-    exists when vjp_ok: a first width of at most N.MLP2_VJP_MAX_HIDDEN1."""
-    model_id = N.MODEL_MLP
-    entry = "dilqr_mlp2_"
+    (csrc/dilqr_mlp2.h): the dilqr_mlp2 descriptor plus (n, m), H1, H2 and the
+    tensors.  Built by NNDynamics.device_model(like, deep=True); stands wherever
+    an MlpModel does (isinstance(., MlpModel) means one hidden layer: this is
+    not a subclass of it).  Its weight gradient has its own call
+    (mlp2_linearize_vjp, csrc/tu_mlp2_vjp.hip; mlp_linearize_vjp stays the
+    one-hidden-layer one) and exists when vjp_ok: a first width of at most
+    N.MLP2_VJP_MAX_HIDDEN1."""
+    entry, Desc = "dilqr_mlp2_", N.Mlp2
+    width_names, layout = "(H1, H2)", "W1 [H1,n+m], b1 [H1], W2 [H2,H1], b2 [H2], W3 [n,H2], b3 [n]"
 
     def __init__(self, n, m, activation, passthrough, W1, b1, W2, b2, W3, b3):
-        H1, H2 = W1.shape[0], W2.shape[0]
-        if (n, m) not in N.LANE_SHAPES or not (1 <= H1 <= N.MLP_MAX_HIDDEN and 1 <= H2 <= N.MLP_MAX_HIDDEN):
-            raise ValueError(f"dilqr: no MLP kernels for (n, m) = {(n, m)}, (H1, H2) = {(H1, H2)}")
-        self.tensors = (W1, b1, W2, b2, W3, b3)
-        if tuple(tuple(t.shape) for t in self.tensors) != ((H1, n + m), (H1,), (H2, H1), (H2,), (n, H2), (n,)):
-            raise ValueError("dilqr: MLP weights must be W1 [H1,n+m], b1 [H1], W2 [H2,H1], b2 [H2], W3 [n,H2], b3 [n]")
-        for t in self.tensors:
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != W1.device or t.data_ptr() % 16:
-                raise ValueError("dilqr: MLP weights must be fp32, contiguous, 16-byte aligned, on one device")
-        self.n, self.m, self.H1, self.H2, self.device = n, m, H1, H2, W1.device
-        self.desc = N.Mlp2(H1, H2, int(activation), int(bool(passthrough)), *(t.data_ptr() for t in self.tensors))
-        self.vjp_ok = H1 <= N.MLP2_VJP_MAX_HIDDEN1     # inside the envelope of dilqr_mlp2_linearize_vjp_f32
-
-    check = MlpModel.check
+        super().__init__(n, m, activation, passthrough, W1, b1, W2, b2, W3, b3)
+        self.H1, self.H2 = self.widths
+        self.vjp_ok = self.H1 <= N.MLP2_VJP_MAX_HIDDEN1  # inside the envelope of dilqr_mlp2_linearize_vjp_f32
 
 
 MLP_MODELS = (MlpModel, Mlp2Model)
@@ -151,29 +163,18 @@ class Dynamics:
                    N.ptr(f), N.stream(x.device))
         return F, f
 
-    def linearize_vjp(self, x, u, gF, gf, dW1, db1, dW2, db2, max_waves=0):
+    def linearize_vjp(self, x, u, gF, gf, *grads, max_waves=0):
         """The gradient of linearize's F, f into the network's weights (the MLP
-        only) for incoming gF, gf (None = zeros), written into dW1 [H,n+m],
-        db1 [H], dW2 [n,H], db2 [n]; the workspace is allocated here."""
+        only; a two-hidden-layer model must be vjp_ok) for incoming gF, gf
+        (None = zeros), written into grads, one tensor per weight in the order
+        and shapes of the model's tensors (dW1, db1, dW2, db2[, dW3, db3]); the
+        workspace is allocated here."""
         T, B = x.shape[:2]
-        nbytes = N.lib().dilqr_mlp_linearize_vjp_ws_bytes(self.n, self.m, T, B, self.mlp.H, int(max_waves))
+        entry = self.mlp.entry + "linearize_vjp_"
+        nbytes = getattr(N.lib(), entry + "ws_bytes")(self.n, self.m, T, B, *self.mlp.widths, int(max_waves))
         ws = torch.empty(max(nbytes // 4, 1), device=x.device)
-        N.call("dilqr_mlp_linearize_vjp_f32", self.n, self.m, T, B, self.mlp.desc, N.ptr(x), N.ptr(u), N.ptr(gF),
-               N.ptr(gf), N.ptr(dW1), N.ptr(db1), N.ptr(dW2), N.ptr(db2), int(max_waves), N.ptr(ws), nbytes,
-               N.stream(x.device))
-
-    def linearize_vjp2(self, x, u, gF, gf, dW1, db1, dW2, db2, dW3, db3, max_waves=0):
-        """linearize_vjp for the two-hidden-layer model (an Mlp2Model with
-        vjp_ok): the six gradients written into dW1 [H1,n+m], db1 [H1],
-        dW2 [H2,H1], db2 [H2], dW3 [n,H2], db3 [n]; the workspace is allocated
-        here."""
-        T, B = x.shape[:2]
-        nbytes = N.lib().dilqr_mlp2_linearize_vjp_ws_bytes(self.n, self.m, T, B, self.mlp.H1, self.mlp.H2,
-                                                           int(max_waves))
-        ws = torch.empty(max(nbytes // 4, 1), device=x.device)
-        N.call("dilqr_mlp2_linearize_vjp_f32", self.n, self.m, T, B, self.mlp.desc, N.ptr(x), N.ptr(u), N.ptr(gF),
-               N.ptr(gf), N.ptr(dW1), N.ptr(db1), N.ptr(dW2), N.ptr(db2), N.ptr(dW3), N.ptr(db3), int(max_waves),
-               N.ptr(ws), nbytes, N.stream(x.device))
+        N.call(entry + "f32", self.n, self.m, T, B, self.mlp.desc, N.ptr(x), N.ptr(u), N.ptr(gF), N.ptr(gf),
+               *(N.ptr(g) for g in grads), int(max_waves), N.ptr(ws), nbytes, N.stream(x.device))
 
     def line_search(self, x_init, C, c, x, u, K, k, bounds, zI, decay, max_ls, x_out, u_out, cost, du_sq, alpha,
                     old_cost=None):
@@ -292,6 +293,34 @@ def mlp_linearize(mlp, x, u):
     return Dynamics(mlp, mlp.n, mlp.m).linearize(x, u)
 
 
+def _linearize_vjp(name, mlp, x, u, gF, gf, max_waves):
+    """mlp_linearize_vjp and mlp2_linearize_vjp (name: the caller's, for the
+    messages) once the kind of model is settled: the argument checks, one
+    gradient per tensor of the model, the launches."""
+    x, u = _al16(_f32(x)), _al16(_f32(u))
+    if x.ndimension() != 3 or u.ndimension() != 3:
+        raise ValueError(f"dilqr: {name} takes x [T,B,n], u [T,B,m]; got {tuple(x.shape)}, {tuple(u.shape)}")
+    mlp.check(x, u)
+    if max_waves < 0:
+        raise ValueError("dilqr: max_waves must be >= 0")
+    T, B = x.shape[:2]
+    n, d = mlp.n, mlp.n + mlp.m
+    gF, gf = (None if g is None else _al16(_f32(g)) for g in (gF, gf))
+    for g, shape, gname in ((gF, (max(T - 1, 0), B, n, d), "gF"), (gf, (max(T - 1, 0), B, n), "gf")):
+        if g is None:
+            continue
+        if tuple(g.shape) != shape:
+            raise ValueError(f"dilqr: {gname} must be {shape}; got {tuple(g.shape)}")
+        if g.device != mlp.device:
+            raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
+    rows = max(T - 1, 0) * B
+    new = torch.zeros if rows == 0 else torch.empty
+    out = tuple(new(*t.shape, device=x.device) for t in mlp.tensors)
+    if rows:
+        Dynamics(mlp, mlp.n, mlp.m).linearize_vjp(x, u, gF, gf, *out, max_waves=max_waves)
+    return out
+
+
 def mlp_linearize_vjp(mlp, x, u, gF, gf, max_waves=0):
     """The backward of mlp_linearize into the weights: (dW1 [H,n+m], db1 [H],
     dW2 [n,H], db2 [n]) for gradients gF [T-1,B,n,n+m] on F and gf [T-1,B,n]
@@ -301,42 +330,38 @@ def mlp_linearize_vjp(mlp, x, u, gF, gf, max_waves=0):
     launched, at T = 1 or B = 0."""
     if not isinstance(mlp, MlpModel):
         raise TypeError("dilqr: mlp_linearize_vjp is built for the one-hidden-layer MlpModel only")
-    x, u = _al16(_f32(x)), _al16(_f32(u))
-    if x.ndimension() != 3 or u.ndimension() != 3:
-        raise ValueError(f"dilqr: mlp_linearize_vjp takes x [T,B,n], u [T,B,m]; got {tuple(x.shape)}, {tuple(u.shape)}")
-    mlp.check(x, u)
-    if max_waves < 0:
-        raise ValueError("dilqr: max_waves must be >= 0")
-    T, B = x.shape[:2]
-    n, d, H = mlp.n, mlp.n + mlp.m, mlp.H
-    gF, gf = (None if g is None else _al16(_f32(g)) for g in (gF, gf))
-    for g, shape, name in ((gF, (max(T - 1, 0), B, n, d), "gF"), (gf, (max(T - 1, 0), B, n), "gf")):
-        if g is None:
-            continue
-        if tuple(g.shape) != shape:
-            raise ValueError(f"dilqr: {name} must be {shape}; got {tuple(g.shape)}")
-        if g.device != mlp.device:
-            raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
-    rows = max(T - 1, 0) * B
-    new = torch.zeros if rows == 0 else torch.empty
-    out = tuple(new(*s, device=x.device) for s in ((H, d), (H,), (n, H), (n,)))
-    if rows:
-        Dynamics(mlp, mlp.n, mlp.m).linearize_vjp(x, u, gF, gf, *out, max_waves=max_waves)
-    return out
+    return _linearize_vjp("mlp_linearize_vjp", mlp, x, u, gF, gf, max_waves)
 
 
-class _MlpLinearizeDiff(torch.autograd.Function):
-    """mlp_linearize with the gradient into the four parameters (W1, b1, W2,
-    b2: the storage the MlpModel points at): the linearisation kernel forward,
-    mlp_linearize_vjp backward.  x and u get no gradient."""
+def mlp2_linearize_vjp(mlp2, x, u, gF, gf, max_waves=0):
+    """mlp_linearize_vjp for the two-hidden-layer Mlp2Model: (dW1 [H1,n+m],
+    db1 [H1], dW2 [H2,H1], db2 [H2], dW3 [n,H2], db3 [n]) for gradients
+    gF [T-1,B,n,n+m] on F and gf [T-1,B,n] on f (None = zeros) at x [T,B,n],
+    u [T,B,m]; three launches, no atomics, the same bits on every run
+    (csrc/tu_mlp2_vjp.hip).  max_waves caps the groups of waves the rows are
+    dealt to (0: the library's defaults); zeros, and nothing launched, at T = 1
+    or B = 0.  The model must be vjp_ok (H1 <= N.MLP2_VJP_MAX_HIDDEN1)."""
+    if not isinstance(mlp2, Mlp2Model):
+        raise TypeError("dilqr: mlp2_linearize_vjp is built for the two-hidden-layer Mlp2Model only")
+    if not mlp2.vjp_ok:
+        raise ValueError(f"dilqr: mlp2_linearize_vjp takes H1 <= {N.MLP2_VJP_MAX_HIDDEN1}; got {mlp2.H1}")
+    return _linearize_vjp("mlp2_linearize_vjp", mlp2, x, u, gF, gf, max_waves)
+
+
+class _LinearizeDiff(torch.autograd.Function):
+    """mlp_linearize with the gradient into the model's parameters (W, b per
+    layer: the storage the model points at): the linearisation kernel forward,
+    the weight gradient backward — vjp names it, mlp_linearize_vjp or
+    mlp2_linearize_vjp, and it is looked up in this module when the backward
+    runs.  x and u get no gradient."""
 
     @staticmethod
-    def forward(ctx, mlp, x, u, W1, b1, W2, b2):
-        ctx.mlp = mlp
+    def forward(ctx, mlp, vjp, x, u, *params):
+        ctx.mlp, ctx.vjp = mlp, vjp
         ctx.set_materialize_grads(False)
         # saved so that an in-place update of a parameter between forward and
         # backward is refused by autograd (the kernels read the live storage)
-        ctx.save_for_backward(x, u, W1, b1, W2, b2)
+        ctx.save_for_backward(x, u, *params)
         F, f = mlp_linearize(mlp, x, u)
         return F, f
 
@@ -344,8 +369,16 @@ class _MlpLinearizeDiff(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gF, gf):
         x, u = ctx.saved_tensors[:2]
-        grads = mlp_linearize_vjp(ctx.mlp, x, u, gF, gf)
-        return (None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
+        grads = globals()[ctx.vjp](ctx.mlp, x, u, gF, gf)
+        return (None,) * 4 + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:]))
+
+
+def _linearize_diff(vjp, mlp, params, count, refusal, x, u):
+    params = tuple(params)
+    if len(params) != count or any(p.data_ptr() != t.data_ptr() or p.shape != t.shape
+                                   for p, t in zip(params, mlp.tensors)):
+        raise ValueError(refusal)
+    return _LinearizeDiff.apply(mlp, vjp, x.detach(), u.detach(), *params)
 
 
 def mlp_linearize_diff(mlp, params, x, u):
@@ -353,11 +386,19 @@ def mlp_linearize_diff(mlp, params, x, u):
     (W1, b1, W2, b2), the Parameters mlp was made from (NNDynamics.fcs); the
     same bits as mlp_linearize.  Not differentiable twice, and not with respect
     to x and u."""
-    params = tuple(params)
-    if len(params) != 4 or any(p.data_ptr() != t.data_ptr() or p.shape != t.shape
-                               for p, t in zip(params, mlp.tensors)):
-        raise ValueError("dilqr: mlp_linearize_diff takes the four parameters (W1, b1, W2, b2) the MlpModel reads")
-    return _MlpLinearizeDiff.apply(mlp, x.detach(), u.detach(), *params)
+    return _linearize_diff("mlp_linearize_vjp", mlp, params, 4, "dilqr: mlp_linearize_diff takes the four "
+                           "parameters (W1, b1, W2, b2) the MlpModel reads", x, u)
+
+
+def mlp2_linearize_diff(mlp2, params, x, u):
+    """mlp_linearize(mlp2, x, u) whose F, f carry the gradient into params =
+    (W1, b1, W2, b2, W3, b3), the Parameters the Mlp2Model was made from
+    (NNDynamics.fcs); the same bits as mlp_linearize.  Not differentiable
+    twice, and not with respect to x and u."""
+    if not isinstance(mlp2, Mlp2Model) or not mlp2.vjp_ok:
+        raise ValueError("dilqr: mlp2_linearize_diff takes an Mlp2Model inside the weight gradient's envelope (vjp_ok)")
+    return _linearize_diff("mlp2_linearize_vjp", mlp2, params, 6, "dilqr: mlp2_linearize_diff takes the six "
+                           "parameters (W1, b1, W2, b2, W3, b3) the Mlp2Model reads", x, u)
 
 
 def mlp_implicit_backward(mlp, dl_dx, dl_du, C, c, x, u, u_lower, u_upper, want_dF=True):
@@ -449,81 +490,6 @@ def mlp_implicit_step(mlp, x_init, C, c, F, f, x, u, u_lower=None, u_upper=None)
     lo = u_lower if (u_lower is None or isinstance(u_lower, (int, float))) else u_lower.detach()
     hi = u_upper if (u_upper is None or isinstance(u_upper, (int, float))) else u_upper.detach()
     return _MlpImplicitStep.apply(mlp, lo, hi, x.detach(), u.detach(), x_init, C, c, F, f)
-
-
-def mlp2_linearize_vjp(mlp2, x, u, gF, gf, max_waves=0):
-    """mlp_linearize_vjp for the two-hidden-layer Mlp2Model: (dW1 [H1,n+m],
-    db1 [H1], dW2 [H2,H1], db2 [H2], dW3 [n,H2], db3 [n]) for gradients
-    gF [T-1,B,n,n+m] on F and gf [T-1,B,n] on f (None = zeros) at x [T,B,n],
-    u [T,B,m]; three launches, no atomics, the same bits on every run
-    (csrc/tu_mlp2_vjp.hip).  max_waves caps the groups of waves the rows are
-    dealt to (0: the library's defaults); zeros, and nothing launched, at T = 1
-    or B = 0.  The model must be vjp_ok (H1 <= N.MLP2_VJP_MAX_HIDDEN1)."""
-    if not isinstance(mlp2, Mlp2Model):
-        raise TypeError("dilqr: mlp2_linearize_vjp is built for the two-hidden-layer Mlp2Model only")
-    if not mlp2.vjp_ok:
-        raise ValueError(f"dilqr: mlp2_linearize_vjp takes H1 <= {N.MLP2_VJP_MAX_HIDDEN1}; got {mlp2.H1}")
-    x, u = _al16(_f32(x)), _al16(_f32(u))
-    if x.ndimension() != 3 or u.ndimension() != 3:
-        raise ValueError(f"dilqr: mlp2_linearize_vjp takes x [T,B,n], u [T,B,m]; got {tuple(x.shape)}, {tuple(u.shape)}")
-    mlp2.check(x, u)
-    if max_waves < 0:
-        raise ValueError("dilqr: max_waves must be >= 0")
-    T, B = x.shape[:2]
-    n, d = mlp2.n, mlp2.n + mlp2.m
-    gF, gf = (None if g is None else _al16(_f32(g)) for g in (gF, gf))
-    for g, shape, name in ((gF, (max(T - 1, 0), B, n, d), "gF"), (gf, (max(T - 1, 0), B, n), "gf")):
-        if g is None:
-            continue
-        if tuple(g.shape) != shape:
-            raise ValueError(f"dilqr: {name} must be {shape}; got {tuple(g.shape)}")
-        if g.device != mlp2.device:
-            raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
-    rows = max(T - 1, 0) * B
-    new = torch.zeros if rows == 0 else torch.empty
-    out = tuple(new(*t.shape, device=x.device) for t in mlp2.tensors)
-    if rows:
-        Dynamics(mlp2, mlp2.n, mlp2.m).linearize_vjp2(x, u, gF, gf, *out, max_waves=max_waves)
-    return out
-
-
-class _Mlp2LinearizeDiff(torch.autograd.Function):
-    """mlp_linearize on an Mlp2Model with the gradient into its six parameters
-    (W1, b1, W2, b2, W3, b3: the storage the model points at): the
-    linearisation kernel forward, mlp2_linearize_vjp backward.  x and u get no
-    gradient."""
-
-    @staticmethod
-    def forward(ctx, mlp2, x, u, *params):
-        ctx.mlp = mlp2
-        ctx.set_materialize_grads(False)
-        # saved so that an in-place update of a parameter between forward and
-        # backward is refused by autograd (the kernels read the live storage)
-        ctx.save_for_backward(x, u, *params)
-        F, f = mlp_linearize(mlp2, x, u)
-        return F, f
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gF, gf):
-        x, u = ctx.saved_tensors[:2]
-        grads = mlp2_linearize_vjp(ctx.mlp, x, u, gF, gf)
-        return (None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
-
-
-def mlp2_linearize_diff(mlp2, params, x, u):
-    """mlp_linearize(mlp2, x, u) whose F, f carry the gradient into params =
-    (W1, b1, W2, b2, W3, b3), the Parameters the Mlp2Model was made from
-    (NNDynamics.fcs); the same bits as mlp_linearize.  Not differentiable
-    twice, and not with respect to x and u."""
-    params = tuple(params)
-    if not isinstance(mlp2, Mlp2Model) or not mlp2.vjp_ok:
-        raise ValueError("dilqr: mlp2_linearize_diff takes an Mlp2Model inside the weight gradient's envelope (vjp_ok)")
-    if len(params) != 6 or any(p.data_ptr() != t.data_ptr() or p.shape != t.shape
-                               for p, t in zip(params, mlp2.tensors)):
-        raise ValueError("dilqr: mlp2_linearize_diff takes the six parameters (W1, b1, W2, b2, W3, b3) the "
-                         "Mlp2Model reads")
-    return _Mlp2LinearizeDiff.apply(mlp2, x.detach(), u.detach(), *params)
 
 
 def rollout(model_id, theta, x_init, u, F=None, f=None):
