@@ -17,10 +17,6 @@ namespace dilqr {
 constexpr int kBlock = 64;   // one wave per workgroup: 64 problems, 4 workgroups per CU
                              // at B=65536, freely distributed over the 8 XCDs.
 constexpr size_t kLdsPerCU = 160 * 1024;   // CDNA4 LDS per CU
-#ifndef DILQR_NO_LDS_GAINS
-#define DILQR_NO_LDS_GAINS 0
-#endif
-constexpr bool kNoLdsGains = DILQR_NO_LDS_GAINS;   // test builds: gain records in HBM always
 
 static inline int grid_for(long long n) { return (int)((n + kBlock - 1) / kBlock); }
 

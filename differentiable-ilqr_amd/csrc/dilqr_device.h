@@ -197,17 +197,6 @@ template <int R, int Cc>
 DEV void ld2(float (&r)[R][Cc], const float* __restrict__ p) {
   ld<R * Cc>(*reinterpret_cast<float(*)[R * Cc]>(&r[0][0]), p);
 }
-// st with non-temporal stores (write-once outputs nothing in the kernel
-// reads back: the implicit backward's dC), K a multiple of 4
-typedef float f4 __attribute__((ext_vector_type(4)));
-template <int K>
-DEV void st_nt(float* __restrict__ p, const float (&r)[K]) {
-  static_assert(K % 4 == 0, "16-byte pieces");
-  f4* q = reinterpret_cast<f4*>(p);
-#pragma unroll
-  for (int i = 0; i < K / 4; ++i) __builtin_nontemporal_store(f4{r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]}, q + i);
-}
-
 template <int R, int Cc>
 DEV void st2(float* __restrict__ p, const float (&r)[R][Cc]) {
   st<R * Cc>(p, *reinterpret_cast<const float(*)[R * Cc]>(&r[0][0]));
@@ -545,14 +534,11 @@ struct DenseF {
 // away (a Jacobian's identity entries).  The values equal the 0-started sum's
 // except for the sign of an exact zero.  Under full unrolling `first` is a
 // compile-time constant.
-#ifndef DILQR_ACC0
-#define DILQR_ACC0 0                        // 1: the 0-started sums (A/B builds)
-#endif
 struct Acc {
   float s = 0.f;
   bool first = true;
   DEV void add(float a, float b) {
-    if (first && !DILQR_ACC0) s = a * b;
+    if (first) s = a * b;
     else s += a * b;
     first = false;
   }

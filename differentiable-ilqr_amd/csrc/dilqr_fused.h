@@ -349,22 +349,6 @@ static_assert(kPFL == 1 || kPFL == 2, "the line search prefetches one or two ste
 #define DILQR_COPY_K 5
 #endif
 constexpr int kCopyK = DILQR_COPY_K;
-// The whole-solve kernels thread a LaneCarry through their phases (0: A/B
-// builds only — every phase loads as the per-launch kernels do).
-#ifndef DILQR_SOLVE_CARRY
-#define DILQR_SOLVE_CARRY 1
-#endif
-constexpr bool kSolveCarry = DILQR_SOLVE_CARRY;
-// ... and run the waves whose costs are all time-invariant diagonal in a loop
-// of their own (k_mpc_solve_fixed; 0: A/B builds only)
-#ifndef DILQR_SOLVE_WAVE_DC
-#define DILQR_SOLVE_WAVE_DC 1
-#endif
-constexpr bool kSolveWaveDc = DILQR_SOLVE_WAVE_DC;
-
-#ifndef DILQR_PHASE_SKIP
-#define DILQR_PHASE_SKIP 0
-#endif
 
 // ---------------- forward: the line search (lqr_step_explicit.py:166-263).
 // Pass p uses alpha_p = decay^p and is accepted when its cost <= old cost or
@@ -753,14 +737,6 @@ DEV int ilqr_problem(int T, int B, int b, const Model md, const float* __restric
     }
   }
   DILQR_STAMP(2);
-#if DILQR_PHASE_SKIP & 1
-  // timing-only builds (tools/small_phase_split.py; never the shipped library):
-  // the iteration ends after the sweep, the trajectory kept, so every iteration
-  // repeats the same sweep and the line search's share is the difference
-  cost_out = old_cost;
-  alpha_out = 1.f;
-  return 0;
-#endif
   if constexpr (!CostT::kDiag && packed_diag_ok<d>()) {
     if (pack_out && sym && diag && tinv) {              // iteration 0 of a diag(q), p over t cost
       CostDiagConst<d> cc;
@@ -896,12 +872,7 @@ DEV LaneIter mpc_iteration_lane(int T, int B, int b, const Model md, const float
     // this wave is flagged kCostDiag | kCostTinv, so this instantiation holds no
     // other cost path (and no join with one: a join makes the compiler wait for
     // whatever any of the paths may have left in flight, trajectory stores included)
-#ifdef DILQR_ONLY_DIAGCONST                // ISA-listing builds only (tools/loop_stats.py)
-    constexpr bool only_dc = true;
-#else
-    constexpr bool only_dc = ONLY_DC;
-#endif
-    if (only_dc || (pk & (kCostDiag | kCostTinv)) == (kCostDiag | kCostTinv)) {
+    if (ONLY_DC || (pk & (kCostDiag | kCostTinv)) == (kCostDiag | kCostTinv)) {
       if constexpr (packed_diag_ok<n + m>()) {
         CostDiagConst<n + m> cc;
         if constexpr (CARRY) cc = cy->cc;                   // begin's pk_first: the record init() reads
@@ -912,7 +883,7 @@ DEV LaneIter mpc_iteration_lane(int T, int B, int b, const Model md, const float
       } else {
         __builtin_unreachable();
       }
-    } else if constexpr (only_dc) {
+    } else if constexpr (ONLY_DC) {
       __builtin_unreachable();
     } else if (pk & kCostDiag) {           // set by iteration 0 only when packed_diag_ok
       if constexpr (packed_diag_ok<n + m>())
@@ -1253,10 +1224,9 @@ __global__ void __launch_bounds__(kBlock, DILQR_SOLVE_OCC) k_mpc_solve_fixed(int
   // (pk = 0) iteration 0 reads the caller's C like the per-launch path
   // the lane's carry: x_init, the cost registers, and the head and tail records
   // of its current trajectory stay in registers from here to the last iteration
-  constexpr bool CY = kSolveCarry;
   LaneCarry<Model> cy;
-  const unsigned pk = S.Cpk ? mpc_begin_lane<Model, true, CY>(T, B, b, md, x_init, u_init, S, C, c, &cy)
-                            : mpc_begin_lane<Model, false, CY>(T, B, b, md, x_init, u_init, S, nullptr, nullptr, &cy);
+  const unsigned pk = S.Cpk ? mpc_begin_lane<Model, true, true>(T, B, b, md, x_init, u_init, S, C, c, &cy)
+                            : mpc_begin_lane<Model, false, true>(T, B, b, md, x_init, u_init, S, nullptr, nullptr, &cy);
   DILQR_STAMP(1);
   LaneIter r{0.f, 0.f, 0};
   int cur = 0, best = 0, best_iter = 0;
@@ -1267,18 +1237,18 @@ __global__ void __launch_bounds__(kBlock, DILQR_SOLVE_OCC) k_mpc_solve_fixed(int
   // diagonal cost path alone (mpc_iteration_lane ONLY_DC)
   auto iterate = [&](auto only_dc) {
     constexpr bool DC = decltype(only_dc)::value;
-    r = mpc_iteration_lane<Model, BM, LG, false, false, kSolveLpw, CY, DC>(T, B, b, md, x_init, C, c, bd, decay,
-                                                                           max_ls, S, S.du_sq, lds_gains, 0, 0, pk,
-                                                                           0.f, nullptr, &cy);
+    r = mpc_iteration_lane<Model, BM, LG, false, false, kSolveLpw, true, DC>(T, B, b, md, x_init, C, c, bd, decay,
+                                                                             max_ls, S, S.du_sq, lds_gains, 0, 0, pk,
+                                                                             0.f, nullptr, &cy);
     cur = best = r.slot;
     best_cost = r.cost;
     DILQR_STAMP(3);
     for (int it = 1; it < iters; ++it) {
       if (it == iters - 1) DILQR_STAMP(4);
-      r = mpc_iteration_lane<Model, BM, LG, false, true, kSolveLpw, CY, DC>(T, B, b, md, x_init, C, c, bd, decay,
-                                                                            max_ls, S, S.du_sq + it * plane,
-                                                                            lds_gains, cur, best, pk, r.cost,
-                                                                            nullptr, &cy);
+      r = mpc_iteration_lane<Model, BM, LG, false, true, kSolveLpw, true, DC>(T, B, b, md, x_init, C, c, bd, decay,
+                                                                              max_ls, S, S.du_sq + it * plane,
+                                                                              lds_gains, cur, best, pk, r.cost,
+                                                                              nullptr, &cy);
       take = mpc_takes_best(false, r.cost, best_cost, best_cost_eps);
       if (take) { best_cost = r.cost; best = r.slot; best_iter = it; }
       cur = r.slot;
@@ -1291,7 +1261,7 @@ __global__ void __launch_bounds__(kBlock, DILQR_SOLVE_OCC) k_mpc_solve_fixed(int
   // iteration; in the shared loop those joins drain the lane's trajectory
   // stores at the start and at the end of every iteration.
   bool wave_dc = false;
-  if constexpr (packed_diag_ok<Model::N + m>() && kSolveWaveDc)
+  if constexpr (packed_diag_ok<Model::N + m>())
     wave_dc = __ballot((pk & (kCostDiag | kCostTinv)) != (kCostDiag | kCostTinv)) == 0ull;
   if (wave_dc) iterate(std::true_type{});
   else iterate(std::false_type{});
@@ -1435,7 +1405,7 @@ __global__ void __launch_bounds__(kSmallMax) k_mpc_solve_small(int T, int B, con
 // batch with a long horizon: the IL loop's T = 35, 4096 problems), and a
 // workgroup's share stays within the 64 KiB a launch may take without opting in.
 inline bool lds_gains_fit(size_t lds, int B) {
-  if (kNoLdsGains || lds > 65536) return false;
+  if (lds > 65536) return false;
   if (lds * 4 <= kLdsPerCU) return true;
   static int cus = [] {
     int dev = 0, n = 0;
@@ -1500,7 +1470,7 @@ int launch_mpc_solve_small_tpp(const MpcSolveArgs& a, float eps, int lim) {
   if (a.B > kSmallMax) return DILQR_E_SHAPE;
   const int threads = (a.B + 63) / 64 * 64;
   const size_t lds = (size_t)a.T * 64 * (MD::N * MD::M + MD::M) * sizeof(float);
-  const bool lg = threads == 64 && lds <= 65536 && !kNoLdsGains;
+  const bool lg = threads == 64 && lds <= 65536;
 #define LAUNCH_SMALL(BM_)                                                                                    \
   do {                                                                                                       \
     if (lg)                                                                                                  \

@@ -130,129 +130,6 @@ DEV void group_gains_col(int j, const float (&Quu)[m][m], const float (&rhs)[m],
   }
 }
 
-// One backward Riccati step for the group's problem; lane r owns rows r of
-// C/Q/P/V.  Crow: C_t row r, cb_r: c_back_t[r] (both only meaningful for r < d).
-// F_t rows are already in L.F (zero for t = T-1), V/v of step t+1 in L.V / L.v.
-// On return the gains are in K/k (all lanes) and L.Kk, V/v of step t in L.
-template <int n, int m, int MODE>
-DEV void group_riccati_step(GroupLds<n, m>& L, int r, const float (&Crow)[n + m], float cb_r,
-                            const float (&zI)[m], const float (&lb)[m], const float (&ub)[m], float (&K)[m][n],
-                            float (&k)[m], float (&prev_k)[m], bool& have_prev, int& n_qp) {
-  constexpr int d = n + m;
-  constexpr int n2 = (n + 1) / 2, d2 = (d + 1) / 2;   // column pairs (the pad columns of V and F are 0)
-  static_assert(2 * d2 <= GroupLds<n, m>::W, "pairs stay inside the padded rows");
-  const bool row = r < d;
-  // P row r = F[:, r]^T V ; q_r = cb_r + F[:, r] . v.  The dense products run
-  // on column pairs (v_pk_fma_f32: two FMAs per lane per instruction); each
-  // element still accumulates in the same order with one fma per term, so the
-  // rounding is that of the scalar loop.
-  float Fcol[n];
-#pragma unroll
-  for (int l = 0; l < n; ++l) Fcol[l] = row ? L.F[l][r] : 0.f;
-  f2 P2[n2];
-#pragma unroll
-  for (int i = 0; i < n2; ++i) P2[i] = f2{0.f, 0.f};
-#pragma unroll
-  for (int l = 0; l < n; ++l) {
-    const f2* Vl = reinterpret_cast<const f2*>(&L.V[l][0]);
-#pragma unroll
-    for (int i = 0; i < n2; ++i) P2[i] = P2[i] + Fcol[l] * Vl[i];
-  }
-  float qr = 0.f;
-#pragma unroll
-  for (int l = 0; l < n; ++l) qr += Fcol[l] * L.v[l];
-  qr = cb_r + qr;
-  // Q row r = C row r + P row r F
-  f2 S2[d2];
-#pragma unroll
-  for (int i = 0; i < d2; ++i) S2[i] = f2{0.f, 0.f};
-#pragma unroll
-  for (int kk = 0; kk < n; ++kk) {
-    const f2* Fk = reinterpret_cast<const f2*>(&L.F[kk][0]);
-    const float p = (kk & 1) ? P2[kk / 2].y : P2[kk / 2].x;
-#pragma unroll
-    for (int i = 0; i < d2; ++i) S2[i] = S2[i] + p * Fk[i];
-  }
-  float Q[d];
-#pragma unroll
-  for (int j = 0; j < d; ++j) Q[j] = Crow[j] + ((j & 1) ? S2[j / 2].y : S2[j / 2].x);
-  if (r >= n && r < d) {
-#pragma unroll
-    for (int j = 0; j < d; ++j) L.Qu[r - n][j] = Q[j];
-    L.Qu[r - n][GroupLds<n, m>::W] = qr;
-  }
-  __syncthreads();
-  float Quu[m][m], qu[m], rhs[m];
-  const int jc = r <= n ? r : n;                 // this lane's right-hand side (lanes > n repeat k's)
-#pragma unroll
-  for (int a = 0; a < m; ++a) {
-#pragma unroll
-    for (int b = 0; b < m; ++b) Quu[a][b] = L.Qu[a][n + b];
-    qu[a] = L.Qu[a][GroupLds<n, m>::W];
-    rhs[a] = jc < n ? L.Qu[a][jc] : qu[a];
-  }
-  float col[m];
-  group_gains_col<n, m, MODE>(jc, Quu, rhs, qu, zI, lb, ub, col, prev_k, have_prev, n_qp);
-  if (r < n) {
-#pragma unroll
-    for (int a = 0; a < m; ++a) L.Kk[a][r] = col[a];
-  } else if (r == n) {
-#pragma unroll
-    for (int a = 0; a < m; ++a) L.Kk[a][GroupLds<n, m>::W] = col[a];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int a = 0; a < m; ++a) {
-#pragma unroll
-    for (int jj = 0; jj < n; ++jj) K[a][jj] = L.Kk[a][jj];
-    k[a] = L.Kk[a][GroupLds<n, m>::W];
-  }
-  if (r < n) {
-    float Kc[m];
-#pragma unroll
-    for (int a = 0; a < m; ++a) Kc[a] = L.Kk[a][r];
-    float KcQuu[m];
-#pragma unroll
-    for (int b = 0; b < m; ++b) {
-      float s = 0.f;
-#pragma unroll
-      for (int a = 0; a < m; ++a) s += Kc[a] * Quu[a][b];
-      KcQuu[b] = s;
-    }
-    // V row r on column pairs, K and Q_ux pairs straight from LDS (the pad
-    // column n of the last pair is computed and dropped)
-    f2 V2[n2];
-#pragma unroll
-    for (int i = 0; i < n2; ++i) {
-      f2 s1 = f2{0.f, 0.f}, s2 = f2{0.f, 0.f}, s3 = f2{0.f, 0.f};
-#pragma unroll
-      for (int a = 0; a < m; ++a) {
-        const f2 Ka = reinterpret_cast<const f2*>(&L.Kk[a][0])[i];
-        const f2 Qa = reinterpret_cast<const f2*>(&L.Qu[a][0])[i];
-        s1 = s1 + Q[n + a] * Ka;
-        s2 = s2 + Kc[a] * Qa;
-        s3 = s3 + KcQuu[a] * Ka;
-      }
-      V2[i] = ((f2{Q[2 * i], Q[2 * i + 1]} + s1) + s2) + s3;
-    }
-    float Vr[n];
-#pragma unroll
-    for (int kk = 0; kk < n; ++kk) Vr[kk] = (kk & 1) ? V2[kk / 2].y : V2[kk / 2].x;
-    float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-    for (int a = 0; a < m; ++a) {
-      s1 += Q[n + a] * k[a];
-      s2 += Kc[a] * qu[a];
-      s3 += KcQuu[a] * k[a];
-    }
-    float vr = ((qr + s1) + s2) + s3;
-    // every lane has finished reading the old V (first barrier above)
-#pragma unroll
-    for (int kk = 0; kk < n; ++kk) L.V[r][kk] = Vr[kk];
-    L.v[r] = vr;
-  }
-}
-
 // ---------------------------------------------------------------- transposed step
 // The Riccati step of the sweeps (k_lqr_backward_group, the fused MPC sweep)
 // with V_{t+1} held in registers, TRANSPOSED: lane l < n keeps column l of
@@ -267,8 +144,8 @@ DEV void group_riccati_step(GroupLds<n, m>& L, int r, const float (&Crow)[n + m]
 // Jacobian in registers, FS = Model::FSparsity: rocket 69 of 208 entries):
 // a zero term adds exactly nothing to an fma chain started at +0 (such a chain
 // never holds -0), so the dense F of the unfused path (FS = DenseF, rows in
-// LDS, DenseF of dilqr_device.h) gives the same bits on finite data.  Replaces per step the old rows-of-V
-// step's two dense 13x13x16 products and its V/F row broadcasts (group_riccati_step).
+// LDS, DenseF of dilqr_device.h) gives the same bits on finite data.  Replaced per step the rows-of-V
+// step's two dense 13x13x16 products and its V/F row broadcasts (since removed).
 template <int n, int m, bool HAS_F, bool HAS_TAU>
 struct GroupLdsT {
   static constexpr int d = n + m;
@@ -641,12 +518,12 @@ DEV float group_forward_pass(LdsT& L, const Model* md, const float* __restrict__
 
 // Where a group's stage cost comes from.  Lane r needs row r of C_t and c_t.
 // Either the caller's C [T,B,d,d], c [T,B,d] (one 64-byte row per lane per
-// step), or — for a problem whose cost the solve's iteration 0 found to be
-// diagonal (every off-diagonal entry +0.0 bit for bit) and the same at every t
-// (the reference's own callers: diag(q), p repeated, il_env.py:159-162) — two
-// registers per lane, C[r][r] and c[r].  row() fills Crow with exactly the
-// values the load returns, so the arithmetic is unchanged, bit for bit; only
-// the bytes are not read (the dense rows were 30 KB per problem and pass).
+// step), or — for a cost that is diagonal (every off-diagonal entry +0.0 bit
+// for bit) and the same at every t — two registers per lane, C[r][r] and c[r];
+// row() then fills Crow with exactly the values the load returns.  No caller
+// sets dconst any more (the MPC sweep that did runs on 8 lanes per problem now,
+// dilqr_group8.h); the fields stay because k_ilqr_iterate_group's instruction
+// schedule changes without them.
 struct GroupCost {
   const float* __restrict__ C;
   const float* __restrict__ c;
@@ -838,22 +715,15 @@ __global__ void __launch_bounds__(64) k_lqr_forward_group(int T, int B, const fl
 // The backward half of ilqr_problem (dilqr_fused.h) for a 16-lane group:
 // on-the-fly Jacobian rows (Model::jac_row), Riccati + the current stage costs;
 // gain records (K_t, k_t, stage cost) go to ws [T,B,GREC].
-// cs: the cost source (GroupCost).  cpk_out / sym_out (the solve's iteration 0,
-// reading the caller's C): decide per problem whether its cost is diagonal and
-// time-invariant (flag 7 in sym_out[b], else 0) and, if so, store its row
-// values [B][2d] (diag, then c) in cpk_out and switch cs to them, so that a line
-// search of this same iteration already takes them from registers.
+// cs: the cost source (GroupCost).
 template <class Model>
 constexpr int group_grec() { return ((Model::M * Model::N + Model::M + 1) + 3) / 4 * 4; }
 
 template <class Model, int MODE, class LdsT>
 DEV void group_sweep(LdsT& L, int T, int B, int b, int r, bool valid, const Model& md,
-                     GroupCost& cs, const float* __restrict__ x, const float* __restrict__ u, const Bounds& bd,
-                     float* __restrict__ ws, float* __restrict__ cpk_out = nullptr,
-                     unsigned char* __restrict__ sym_out = nullptr) {
+                     const GroupCost& cs, const float* __restrict__ x, const float* __restrict__ u, const Bounds& bd,
+                     float* __restrict__ ws) {
   constexpr int n = Model::N, m = Model::M, d = n + m;
-  bool ok_diag = true, ok_tinv = true;     // this lane's row: off-diagonal +0.0, equal to step T-1's
-  float cd_last = 0.f, cc_last = 0.f;
   constexpr int GREC = group_grec<Model>();
   float U[n];                              // column r of V_{t+1} (lane n: v_{t+1}), group_riccati_step_t
 #pragma unroll
@@ -870,16 +740,6 @@ DEV void group_sweep(LdsT& L, int T, int B, int b, int r, bool valid, const Mode
     ld(xt, x + tb * n);                              // the group's 16 lanes read the same 64 B
     ld(ut, u + tb * m);
     cs.row(tb, r, Crow, cr);
-    if (cpk_out) {                                   // iteration 0: is the cost a time-invariant diagonal?
-      float dg = 0.f;
-#pragma unroll
-      for (int j = 0; j < d; ++j) {
-        if (j == r) dg = Crow[j];
-        else ok_diag &= __float_as_uint(Crow[j]) == 0u;
-      }
-      if (LAST) { cd_last = dg; cc_last = cr; }
-      ok_tinv &= __float_as_uint(dg) == __float_as_uint(cd_last) && __float_as_uint(cr) == __float_as_uint(cc_last);
-    }
     float tau[d];
 #pragma unroll
     for (int i = 0; i < n; ++i) tau[i] = xt[i];
@@ -924,18 +784,6 @@ DEV void group_sweep(LdsT& L, int T, int B, int b, int r, bool valid, const Mode
   };
   step(T - 1, std::true_type{});
   for (int t = T - 2; t >= 0; --t) step(t, std::false_type{});
-  if (cpk_out) {
-    // the group's verdict (all 16 rows), then the record and the flag; this
-    // iteration's line search reads the registers already
-    const unsigned long long bad = __ballot(!(ok_diag && ok_tinv));
-    const bool grp = ((bad >> (threadIdx.x & ~(kG - 1))) & ((1ull << kG) - 1)) == 0ull;
-    if (valid) {
-      cpk_out[(size_t)b * 2 * d + r] = cd_last;
-      cpk_out[(size_t)b * 2 * d + d + r] = cc_last;
-      if (r == 0) sym_out[b] = grp ? 7 : 0;
-    }
-    if (grp) { cs.dconst = true; cs.cd = cd_last; cs.cc = cc_last; }
-  }
 }
 
 // ilqr_problem (dilqr_fused.h) for a 16-lane group: group_sweep, then the

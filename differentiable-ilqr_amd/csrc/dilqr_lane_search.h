@@ -82,16 +82,12 @@ DEV float lane_stage_cost(const float (&tau)[d], const float (&cd)[d], const flo
   return tree16(pr);
 }
 
-// One pass of this lane's candidate (step size al; lane pair (A, B) of a
-// problem: passes 2p and 2p+1 of the search), its stage costs summed into
+// One pass of this lane's candidate (step size al), its stage costs summed into
 // cost and the current trajectory's (from the gain records) into old_cost.
 // DCONST: the whole wave's problems hold a time-invariant diagonal cost in
 // registers (cd, cc), else every lane reads the caller's rows (a flagged
 // problem's rows hold the same values).  Writes x/u to (xo, uo) when `wr`.
-#ifndef DILQR_SEARCH_PFD
-#define DILQR_SEARCH_PFD 1
-#endif
-template <class Model, int BM, bool DCONST, int PFD = DILQR_SEARCH_PFD>
+template <class Model, int BM, bool DCONST, int PFD>
 DEV void lane_pass(int T, int B, int b, const Model& md, const float* __restrict__ x_init,
                    const float (&cd)[Model::N + Model::M], const float (&cc)[Model::N + Model::M],
                    const float* __restrict__ C, const float* __restrict__ c, const float* __restrict__ ws,
@@ -147,10 +143,11 @@ DEV void lane_pass(int T, int B, int b, const Model& md, const float* __restrict
   };
   // a ring of PFD + 1 input buffers: step t+PFD's loads in flight while step
   // t computes (the loop unrolled PFD + 1 times, so the buffers rotate by
-  // name, no copies).  Measured at config 3 (tools/ab_rocket.py, one box):
-  // PFD 1 0.339-0.351 ms per MPC iteration, 2 0.356-0.368, 3 0.358-0.364 —
-  // a search round streams ~360 MB (gain records, the current trajectory, two
-  // candidates out) at ~5 TB/s, so deeper prefetch only adds registers.
+  // name, no copies).  Measured at config 3 with the pair search since removed
+  // (one box): PFD 1 0.339-0.351 ms per MPC iteration, 2 0.356-0.368, 3
+  // 0.358-0.364 — a search round streamed ~360 MB (gain records, the current
+  // trajectory, two candidates out) at ~5 TB/s, so deeper prefetch only adds
+  // registers; the quad search runs at DILQR_QUAD_PFD.
   constexpr int P = PFD + 1;
   LaneIn<n, m, GREC> ring[P];
 #pragma unroll
@@ -169,95 +166,28 @@ DEV void lane_pass(int T, int B, int b, const Model& md, const float* __restrict
   old_cost = oldc;
 }
 
-// The MPC iteration's line search, one problem per LANE PAIR: lane 2b+0 rolls
-// candidate A (alpha) of problem b, lane 2b+1 candidate B (alpha * decay) —
-// passes 2p and 2p+1 of the search, as in group_ilqr_problem — into slots sa /
-// sb; the pair swaps costs and both take the same decision; then lane A does
-// the best-iterate bookkeeping of k_mpc_iterate.  (Both candidates as f2 in
-// one lane measured slower: 512 waves for 1024 SIMDs at config 3, 54 % of
-// wave time waiting on loads.)  Runs after the group sweep of the same
-// iteration (k_mpc_sweep_group), which published the stop rule's decision
-// (ctrl[iteration & 1]) and, at iteration 0, the cost flags.
-template <class Model, int BM, bool DCONST>
-__global__ void __launch_bounds__(64) k_mpc_search_lane(int T, int B, const float* __restrict__ theta,
-                                                        const float* __restrict__ x_init,
-                                                        const float* __restrict__ C, const float* __restrict__ c,
-                                                        Bounds bd, float decay, int max_ls, int iteration,
-                                                        float best_cost_eps, int G, MpcState S) {
-  constexpr int n = Model::N, m = Model::M, d = n + m;
-  if (iteration > 0 && G >= 0 && S.ctrl[iteration & 1].stopped) return;
-  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-  const int b = tid >> 1, cand = tid & 1;
-  if (b >= B) return;                                          // both lanes of a pair
-  Model md; md.load(theta);
-  const bool first = iteration == 0;
-  const size_t TBn = (size_t)T * B * n, TBm = (size_t)T * B * m;
-  const int cur = S.slot[b], best = S.slot[B + b];
-  int sa, sb;
-  free_slots(cur, best, sa, sb);
-  const int so = cand ? sb : sa;
-  const float* x = S.Xs + cur * TBn;
-  const float* u = S.Us + cur * TBm;
-  float* xo = S.Xs + so * TBn;
-  float* uo = S.Us + so * TBm;
-  const bool dconst = S.Cpk && S.cost_sym[b] == 7;
-  float cd[d], cc[d];
-#pragma unroll
-  for (int r = 0; r < d; ++r) { cd[r] = 0.f; cc[r] = 0.f; }
-  if (dconst) {
-    ld(cd, S.Cpk + (size_t)b * 2 * d);
-    ld(cc, S.Cpk + (size_t)b * 2 * d + d);
-  }
-  // the register cost when every problem of the wave has one (wave-uniform);
-  // the two kinds of wave run in two instantiations (launched back to back,
-  // each leaves the other's waves at once), so that the dense-cost rollout's
-  // registers do not weigh on the common one
-  if (__all(dconst) != DCONST) return;
-  float alpha = 1.f, cost = 0.f, old_cost = 0.f;
-  int win = 0;
-  for (int p = 0; p < max_ls; p += 2) {
-    const bool twoB = p + 1 < max_ls;
-    const float aA = alpha, aB = alpha * decay;
-    const float al = cand ? aB : aA;
-    const bool wr = !cand || twoB;                             // B rolls out only if pass p+1 exists
-    float cm, oc;
-    float* dq = (p == 0 && !cand) ? S.du_sq : nullptr;
-    lane_pass<Model, BM, DCONST>(T, B, b, md, x_init, cd, cc, C, c, S.ws, x, u, bd, al, wr, xo, uo, dq, cm, oc);
-    const float co = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(cm), 0xB1, 0xF, 0xF, false));
-    const float cA = cand ? co : cm, cB = cand ? cm : co;
-    if (p == 0) old_cost = oc;
-    if (!(cA > old_cost) || p == max_ls - 1) { cost = cA; alpha = aA; win = 0; break; }
-    if (!(cB > old_cost) || p + 1 == max_ls - 1) { cost = cB; alpha = aB; win = 1; break; }
-    alpha = aB * decay;                                       // lqr_step_explicit.py:249
-  }
-  if (cand) return;
-  const int nw = win ? sb : sa;
-  S.cost[b] = cost;
-  S.alpha[b] = alpha;
-  const bool better = !first && (cost <= S.best_cost[b] + best_cost_eps);   // mpc_explicit.py:278
-  if (first || better) {
-    S.best_cost[b] = cost;
-    S.slot[B + b] = (unsigned char)nw;
-  }
-  S.improved[b] = (first || better) ? (better ? 2 : 1) : 0;
-  if (S.best_iter && (first || better)) S.best_iter[b] = iteration;       // fixed-count solves
-  S.slot[b] = (unsigned char)nw;
-}
-
-// The same line search on a QUAD of lanes per problem (16 problems per wave):
-// lane j of the quad rolls pass p = 4r + j of round r out for its COST only, so
-// one round decides up to four passes and the gain records and the current
-// trajectory are read once per round for all of them (the quad's lanes read
-// the same addresses).  Pass 0 (lane 0) also writes its trajectory to slot sa,
-// speculatively: it is the winner in most early iterations.  The last pass
-// (p = max_ls - 1) is accepted whatever its cost (lqr_step_explicit.py:252), so
-// it is never rolled out to be compared.  When the winner is not pass 0, lane 0
-// of the quad rolls the winner's step size out again with writes (phase 2; the
-// same function on the same inputs: the same bits).  So the search returns the
-// sequential search's pass, cost, step size and trajectory bit for bit, like
-// k_mpc_search_lane, with one round (and at most one rewrite) where the pairs
-// took up to three rounds (max_ls = 5), two waves per SIMD at config 3 where
-// the pairs had one, and no second candidate stream to HBM.
+// The MPC iteration's line search on a QUAD of lanes per problem (16 problems
+// per wave): lane j of the quad rolls pass p = 4r + j of round r out for its
+// COST only, so one round decides up to four passes and the gain records and
+// the current trajectory are read once per round for all of them (the quad's
+// lanes read the same addresses).  Pass 0 (lane 0) also writes its trajectory
+// to slot sa, speculatively: it is the winner in most early iterations.  The
+// last pass (p = max_ls - 1) is accepted whatever its cost
+// (lqr_step_explicit.py:252), so it is never rolled out to be compared.  The
+// quad shares its costs (ballot + shuffle) and every lane takes the same
+// decision: the first pass whose cost does not exceed the current
+// trajectory's, as in group_ilqr_problem.  When the winner is not pass 0, lane
+// 0 of the quad rolls the winner's step size out again with writes (phase 2;
+// the same function on the same inputs: the same bits).  So the search returns
+// the sequential search's pass, cost, step size and trajectory bit for bit;
+// then lane 0 does the best-iterate bookkeeping of k_mpc_iterate.  Runs after
+// the sweep of the same iteration (k_mpc_sweep_g8), which published the stop
+// rule's decision (ctrl[iteration & 1]) and, at iteration 0, the cost flags.
+// (Measured and removed: one problem per lane PAIR, two passes per round — up
+// to three rounds at max_ls = 5 where the quad takes one, one wave per SIMD at
+// config 3 where the quad has two, and a second candidate stream to HBM; and
+// both candidates as f2 in one lane — 512 waves for 1024 SIMDs at config 3,
+// 54 % of wave time waiting on loads.)
 // the quad search's prefetch distance (0: its two waves per SIMD hide the loads)
 // and its launch-bounds floor
 #ifndef DILQR_QUAD_PFD
@@ -290,7 +220,11 @@ DEV void search_quad_problem(int T, int B, int tid, const Model& md, const float
     ld(cd, S.Cpk + (size_t)b * 2 * d);
     ld(cc, S.Cpk + (size_t)b * 2 * d + d);
   }
-  if (__all(dconst) != DCONST) return;                         // wave-uniform, as k_mpc_search_lane
+  // the register cost when every problem of the wave has one (wave-uniform);
+  // the two kinds of wave run in two instantiations (launched back to back,
+  // each leaves the other's waves at once), so that the dense-cost rollout's
+  // registers do not weigh on the common one
+  if (__all(dconst) != DCONST) return;
   const int q0 = (threadIdx.x & 63) & ~3;                      // the quad's first lane
   const int last = max_ls - 1;
   // alpha_p = decay^p by the sequential search's chain of products (249)

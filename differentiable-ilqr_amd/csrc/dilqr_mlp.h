@@ -11,11 +11,10 @@
 // n*d + n + d accumulators.  W1 [H,d], b1 [H], W2 [n,H], b2 [n] are torch's
 // nn.Linear layouts, read in place.
 //
-// Weight reads (both measured): by default through the constant
-// address space — the addresses are wave-uniform, so the compiler issues scalar
-// loads and the weights never occupy vector registers; with -DDILQR_MLP_LDS=1
-// each workgroup stages them once in LDS and every lane reads the same LDS
-// address (a broadcast).
+// Weight reads: through the constant address space — the addresses are
+// wave-uniform, so the compiler issues scalar loads and the weights never
+// occupy vector registers.  (Staging them in LDS once per workgroup was
+// measured and lost)
 #pragma once
 #include <type_traits>
 
@@ -25,24 +24,13 @@ namespace dilqr {
 
 constexpr int kMlpMaxHidden = DILQR_MLP_MAX_HIDDEN;
 
-#ifndef DILQR_MLP_LDS
-#define DILQR_MLP_LDS 0
-#endif
-
 // the model as the kernels receive it (by value, a kernel argument)
 struct MlpArg {
   int H, passthrough;
   const float *W1, *b1, *W2, *b2;
 };
 
-#if DILQR_MLP_LDS
-typedef const float* MlpW;
-// floats a workgroup stages: W1, b1, W2, b2
-inline size_t mlp_lds_bytes(int n, int m, int H) { return sizeof(float) * ((size_t)H * (n + m) + H + (size_t)n * H + n); }
-#else
 typedef const __attribute__((address_space(4))) float* MlpW;
-inline size_t mlp_lds_bytes(int, int, int) { return 0; }
-#endif
 
 template <int N_, int M_, int ACT>
 struct Mlp {
@@ -56,28 +44,7 @@ struct Mlp {
   DEV void load(const MlpArg& a) {
     H = a.H;
     pt = a.passthrough != 0;
-#if DILQR_MLP_LDS
-    extern __shared__ float mlp_lds[];
-    float* s = mlp_lds;
-    // the lanes still active copy (a tail workgroup has fewer than 64): lane of
-    // rank r among them takes elements r, r + active, ...
-    const unsigned long long act = __ballot(1);
-    const int lane = threadIdx.x & 63;
-    const int r = __popcll(act & ((1ull << lane) - 1ull)), na = __popcll(act);
-    const float* src[4] = {a.W1, a.b1, a.W2, a.b2};
-    const int cnt[4] = {H * D, H, N * H, N};
-    float* dst[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      dst[q] = s;
-      for (int i = r; i < cnt[q]; i += na) s[i] = src[q][i];
-      s += cnt[q];
-    }
-    __syncthreads();
-    W1 = dst[0]; b1 = dst[1]; W2 = dst[2]; b2 = dst[3];
-#else
     W1 = (MlpW)a.W1; b1 = (MlpW)a.b1; W2 = (MlpW)a.W2; b2 = (MlpW)a.b2;
-#endif
   }
 
   // a = act(z), g = act'(z) as grad_input forms it from a (dynamics.py:107-118)

@@ -6,8 +6,7 @@
 // formed from the activation as Mlp::activate does (dilqr_mlp.h).
 //
 // Mapping: one row (problem) per lane, as for Mlp; every weight is read through
-// the constant address space at a wave-uniform address (scalar loads), whatever
-// DILQR_MLP_LDS says (that variant stages the one-layer model only).
+// the constant address space at a wave-uniform address (scalar loads).
 //
 // Layer 1: a1_j = act(b1_j + W1_j . tau) for j < H1, written to the lane's own
 // column of a dynamic-LDS array [H1][64] (256 H1 bytes per one-wave workgroup;

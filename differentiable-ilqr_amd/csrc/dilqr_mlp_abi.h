@@ -47,7 +47,7 @@ struct OneHidden {
     return mlp_check_desc(n, m, {p.W1, p.b1, p.W2, p.b2}, {p.n_hidden}, p.activation);
   }
   static Arg arg(const Desc& p) { return Arg{p.n_hidden, p.passthrough, p.W1, p.b1, p.W2, p.b2}; }
-  static size_t lds_bytes(int n, int m, const Arg& a) { return mlp_lds_bytes(n, m, a.H); }
+  static size_t lds_bytes(int, int, const Arg&) { return 0; }
 };
 
 // two hidden layers: dilqr_mlp2, the model of dilqr_mlp2.h

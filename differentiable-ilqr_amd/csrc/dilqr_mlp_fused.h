@@ -235,9 +235,8 @@ __global__ void __launch_bounds__(kSmallMax) k_mlp_mpc_solve_small(int T, int B,
 // ---------------------------------------------------------------- launchers
 template <int N_, int M_>
 int launch_mlp_ilqr_iterate(const MlpIterArgs& a, int activation) {
-  const size_t lds = mlp_lds_bytes(N_, M_, a.mlp.H);
 #define LAUNCH_IT2(MD_, BM_, PREV_)                                                                           \
-  k_mlp_ilqr_iterate<MD_, BM_, PREV_><<<grid_for(a.B), kBlock, lds, a.stream>>>(                              \
+  k_mlp_ilqr_iterate<MD_, BM_, PREV_><<<grid_for(a.B), kBlock, 0, a.stream>>>(                                \
       a.T, a.B, a.mlp, a.x_init, a.C, a.c, a.x, a.u, a.bd, a.decay, a.max_ls, a.ws, a.x_out, a.u_out, a.cost, \
       a.du_sq, a.alpha, a.old_cost, a.ctrl)
 #define LAUNCH_IT(MD_, BM_)                    \
@@ -268,9 +267,8 @@ int launch_mlp_mpc_solve_small(const MlpSolveArgs& a, int activation) {
     return DILQR_E_SHAPE;
   } else {
   const int threads = (a.B + 63) / 64 * 64;
-  const size_t lds = mlp_lds_bytes(N_, M_, a.mlp.H);
 #define LAUNCH_SMALL(MD_, BM_)                                                                                  \
-  k_mlp_mpc_solve_small<MD_, BM_><<<1, threads, lds, a.stream>>>(a.T, a.B, a.mlp, a.x_init, a.u_init, a.C, a.c, \
+  k_mlp_mpc_solve_small<MD_, BM_><<<1, threads, 0, a.stream>>>(a.T, a.B, a.mlp, a.x_init, a.u_init, a.C, a.c,   \
                                                                  a.bd, a.decay, a.max_ls, a.iters,              \
                                                                  a.best_cost_eps, a.eps, a.lim, a.S)
 #define LAUNCH_MD(MD_)                                                                   \

@@ -38,23 +38,6 @@ template <class Model> struct ImplicitWs {
   static DEV size_t y_off(int T, int B) { return ((size_t)T * B * G + 3) / 4 * 4; }
 };
 
-// DILQR_IMPL_SKIP: timing-only builds (tools/ab.sh variants, never the shipped
-// library) that leave out pass C (bit 0) and/or pass D (bit 1), to split the
-// kernel's time by pass as rocket's group kernel does, or pass D's generated
-// pieces (bit 2 lag_hess, bit 3 lag_dparam, bit 4 f_theta_cs: zeros instead)
-#ifndef DILQR_IMPL_SKIP
-#define DILQR_IMPL_SKIP 0
-#endif
-#ifndef DILQR_IMPL_PFD
-#define DILQR_IMPL_PFD 1
-#endif
-#ifndef DILQR_IMPL_PFB
-#define DILQR_IMPL_PFB 1
-#endif
-#ifndef DILQR_IMPL_PFC
-#define DILQR_IMPL_PFC 0
-#endif
-
 template <class Model>
 __global__ void __launch_bounds__(kBlock) k_implicit_backward(
     int T, int B, const float* __restrict__ theta, const float* __restrict__ C, const float* __restrict__ c,
@@ -101,51 +84,29 @@ __global__ void __launch_bounds__(kBlock) k_implicit_backward(
     float lam[n];
 #pragma unroll
     for (int i = 0; i < n; ++i) lam[i] = 0.f;
-#if DILQR_IMPL_PFB
     // step t-1's x, u and loss gradients loaded while step t computes (1, the
     // shipped setting: config 4 0.220 -> 0.207 ms; 2, C_t and c_t too: 28
     // AGPRs, 0.213 ms — profiles/r06/ab_implicit_cartpole_prefetch.txt)
     struct BIn {
       float x[n], u[m], gx[n], gu[m];
-#if DILQR_IMPL_PFB > 1
-      float C[d][d], c[d];
-#endif
     };
     auto load_b = [&](int t, BIn& in) {
       const size_t tb = (size_t)t * B + b;
       ld(in.x, x + tb * n); ld(in.u, u + tb * m); ld(in.gx, dl_dx + tb * n); ld(in.gu, dl_du + tb * m);
-#if DILQR_IMPL_PFB > 1
-      ld2(in.C, C + tb * d * d); ld(in.c, c + tb * d);
-#endif
     };
     BIn bin;
     load_b(T - 1, bin);
-#endif
     for (int t = T - 1; t >= 0; --t) {
       size_t tb = (size_t)t * B + b;
       float Ct[d][d], ct[d], xt[n], ut[m], gxx[n], gu[m];
-#if DILQR_IMPL_PFB
       BIn bnx;
       load_b(t > 0 ? t - 1 : 0, bnx);
 #pragma unroll
       for (int i = 0; i < n; ++i) { xt[i] = bin.x[i]; gxx[i] = bin.gx[i]; }
 #pragma unroll
       for (int a = 0; a < m; ++a) { ut[a] = bin.u[a]; gu[a] = bin.gu[a]; }
-#if DILQR_IMPL_PFB > 1
-#pragma unroll
-      for (int i = 0; i < d; ++i) {
-        ct[i] = bin.c[i];
-#pragma unroll
-        for (int j = 0; j < d; ++j) Ct[i][j] = bin.C[i][j];
-      }
-#else
       ld2(Ct, C + tb * d * d); ld(ct, c + tb * d);
-#endif
       bin = bnx;
-#else
-      ld2(Ct, C + tb * d * d); ld(ct, c + tb * d); ld(xt, x + tb * n); ld(ut, u + tb * m);
-      ld(gxx, dl_dx + tb * n); ld(gu, dl_du + tb * m);
-#endif
       if (t == T - 1) {
 #pragma unroll
         for (int i = 0; i < d; ++i) { cdiag[i] = Ct[i][i]; cvec[i] = ct[i]; }
@@ -208,35 +169,11 @@ __global__ void __launch_bounds__(kBlock) k_implicit_backward(
     float yx[n];
 #pragma unroll
     for (int i = 0; i < n; ++i) yx[i] = 0.f;
-#if DILQR_IMPL_PFC
-    struct CIn {
-      float x[n], u[m], g[G];
-    };
-    auto load_c = [&](int t, CIn& in) {
-      const size_t tb = (size_t)t * B + b;
-      ld(in.x, x + tb * n); ld(in.u, u + tb * m);
-      SoaRec<G>::load(in.g, wsG, T, t, B, b);
-    };
-    CIn cpre;
-    load_c(0, cpre);
-#endif
-    for (int t = 0; t < ((DILQR_IMPL_SKIP & 1) ? 0 : T); ++t) {
+    for (int t = 0; t < T; ++t) {
       size_t tb = (size_t)t * B + b;
       float xt[n], ut[m], gr[G];
-#if DILQR_IMPL_PFC
-      CIn cnx;
-      load_c(t + 1 < T ? t + 1 : t, cnx);
-#pragma unroll
-      for (int i = 0; i < n; ++i) xt[i] = cpre.x[i];
-#pragma unroll
-      for (int a = 0; a < m; ++a) ut[a] = cpre.u[a];
-#pragma unroll
-      for (int i = 0; i < G; ++i) gr[i] = cpre.g[i];
-      cpre = cnx;
-#else
       ld(xt, x + tb * n); ld(ut, u + tb * m);
       SoaRec<G>::load(gr, wsG, T, t, B, b);
-#endif
       float y[d];
 #pragma unroll
       for (int i = 0; i < n; ++i) y[i] = yx[i];
@@ -271,7 +208,6 @@ __global__ void __launch_bounds__(kBlock) k_implicit_backward(
     for (int a = 0; a < m; ++a) au[a] = 0.f;
 #pragma unroll
     for (int k = 0; k < p; ++k) dth[k] = 0.f;
-#if DILQR_IMPL_PFD
     // step t-1's per-step inputs are loaded while step t computes (one wave per
     // SIMD: nothing else covers the loads' latency); the index clamps at 0, so
     // the load is unconditional (a conditional one drains the queue at its merge).
@@ -288,14 +224,11 @@ __global__ void __launch_bounds__(kBlock) k_implicit_backward(
     };
     DIn cin;
     load_in(T - 1, cin);
-#endif
-    for (int t = (DILQR_IMPL_SKIP & 2) ? -1 : T - 1; t >= 0; --t) {
+    for (int t = T - 1; t >= 0; --t) {
       size_t tb = (size_t)t * B + b;
       float Ct[d][d], ct[d], xt[n], ut[m], gxx[n], gu[m], y[d];
-#if DILQR_IMPL_PFD
       DIn nin;
       load_in(t > 0 ? t - 1 : 0, nin);
-#endif
       if (c_regs) {
 #pragma unroll
         for (int i = 0; i < d; ++i)
@@ -310,18 +243,12 @@ __global__ void __launch_bounds__(kBlock) k_implicit_backward(
       } else {
         ld(ct, c + tb * d);
       }
-#if DILQR_IMPL_PFD
 #pragma unroll
       for (int i = 0; i < n; ++i) { xt[i] = cin.x[i]; gxx[i] = cin.gx[i]; }
 #pragma unroll
       for (int a = 0; a < m; ++a) { ut[a] = cin.u[a]; gu[a] = cin.gu[a]; }
 #pragma unroll
       for (int i = 0; i < d; ++i) y[i] = cin.y[i];
-#else
-      ld(xt, x + tb * n); ld(ut, u + tb * m);
-      ld(gxx, dl_dx + tb * n); ld(gu, dl_du + tb * m);
-      SoaRec<d>::load(y, wsY, T, t, B, b);
-#endif
       float tau[d];
 #pragma unroll
       for (int i = 0; i < n; ++i) tau[i] = xt[i];
@@ -345,30 +272,12 @@ __global__ void __launch_bounds__(kBlock) k_implicit_backward(
       // Krev = K[t] of the reversed stack = K_{T-1-t}: the gain grad_input pairs with step t+1
       if (t < T - 1) {
         float Kq[m][n], Mt[d][d], Mp[d][p];
-#if DILQR_IMPL_PFD
 #pragma unroll
         for (int a = 0; a < m; ++a)
 #pragma unroll
           for (int j = 0; j < n; ++j) Kq[a][j] = cin.K[a][j];
-#else
-        ld2(Kq, K + ((size_t)(T - 1 - t) * B + b) * m * n);
-#endif
-#if DILQR_IMPL_SKIP & 4
-#pragma unroll
-        for (int i = 0; i < d; ++i)
-#pragma unroll
-          for (int j = 0; j < d; ++j) Mt[i][j] = 0.f;
-#else
         D2::lag_hess(theta, xt, ut, lam, cn, sn, Mt);  // lam = lam_{t+1}
-#endif
-#if DILQR_IMPL_SKIP & 8
-#pragma unroll
-        for (int i = 0; i < d; ++i)
-#pragma unroll
-          for (int j = 0; j < p; ++j) Mp[i][j] = 0.f;
-#else
         D2::lag_dparam(theta, xt, ut, lam, cn, sn, Mp);
-#endif
         // w_t = g_t - M_t^T y_t
 #pragma unroll
         for (int k = 0; k < n; ++k) {
@@ -460,14 +369,7 @@ __global__ void __launch_bounds__(kBlock) k_implicit_backward(
 #pragma unroll
         for (int l = 0; l < n; ++l) mu[l] = hx[l] - dlam[l];
         float ft[n][p];
-#if DILQR_IMPL_SKIP & 16
-#pragma unroll
-        for (int i = 0; i < n; ++i)
-#pragma unroll
-          for (int j = 0; j < p; ++j) ft[i][j] = 0.f;
-#else
         D2::f_theta_cs(theta, xt, ut, cn, sn, ft);
-#endif
 #pragma unroll
         for (int k = 0; k < p; ++k) {
           float s = 0.f;
@@ -494,9 +396,7 @@ __global__ void __launch_bounds__(kBlock) k_implicit_backward(
           au[a] = s;
         }
       }
-#if DILQR_IMPL_PFD
       cin = nin;
-#endif
     }
     if (valid) st(dtheta + (size_t)b * p, dth);
   }

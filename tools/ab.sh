@@ -8,6 +8,7 @@ export DILQR_SKIP_BUILD_ID=1   # the variants are built from other sources on pu
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 L=differentiable-ilqr_amd/dilqr/libdilqr.so
 cp $L ab/.inplace.so
+trap 'cp ab/.inplace.so "$L"' EXIT   # restore the in-tree library on any exit
 for r in $(seq ${1:-3}); do
   for f in ab/${AB_GLOB:-libdilqr_*.so}; do
     v=${f#ab/libdilqr_}; v=${v%.so}
@@ -16,4 +17,3 @@ for r in $(seq ${1:-3}); do
     echo "$v $out"
   done
 done
-cp ab/.inplace.so $L

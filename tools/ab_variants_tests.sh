@@ -7,6 +7,7 @@ export DILQR_SKIP_BUILD_ID=1
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 L=differentiable-ilqr_amd/dilqr/libdilqr.so
 cp $L ab/.inplace.so
+trap 'cp ab/.inplace.so "$L"' EXIT   # restore the in-tree library on any exit
 K=${AB_TEST_K:-"fused_iteration_equals_unfused or whole_solve or fixed_count or packed_cost or small_batch or mpc_solve_vs_oracle"}
 rc=0
 for f in ab/${AB_GLOB:-libdilqr_*.so}; do
@@ -17,5 +18,4 @@ for f in ab/${AB_GLOB:-libdilqr_*.so}; do
   echo "$v tests rc=$rc: $(tail -1 gpurun_out/abtest_$v.log)"
   [ $rc -eq 0 ] || break
 done
-cp ab/.inplace.so $L
 exit $rc

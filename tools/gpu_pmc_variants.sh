@@ -6,6 +6,7 @@ export DILQR_SKIP_BUILD_ID=1
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 L=differentiable-ilqr_amd/dilqr/libdilqr.so
 cp $L ab/.inplace.so
+trap 'cp ab/.inplace.so "$L"' EXIT   # restore the in-tree library on any exit
 rc=0
 for f in ab/libdilqr_*.so; do
   v=${f#ab/libdilqr_}; v=${v%.so}
@@ -16,5 +17,4 @@ for f in ab/libdilqr_*.so; do
   echo "$v pmc rc=$rc"
   [ $rc -eq 0 ] || break
 done
-cp ab/.inplace.so $L
 exit $rc

@@ -8,6 +8,7 @@ R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd $R
 L=differentiable-ilqr_amd/dilqr/libdilqr.so
 cp $L ab/.inplace.so
+trap 'cp ab/.inplace.so "$L"' EXIT   # restore the in-tree library on any exit
 for f in ab/${AB_GLOB:-libdilqr_*.so}; do
   v=${f#ab/libdilqr_}; v=${v%.so}
   cp $f $L
@@ -15,4 +16,3 @@ for f in ab/${AB_GLOB:-libdilqr_*.so}; do
       --output-format csv -- python3 $R/${PROF_CMD:-tools/ab_rocket_dense.py} > $R/gpurun_out/pv_$v.log 2>&1) || { cp ab/.inplace.so $L; exit 1; }
   echo "== $v"; f2=$(find gpurun_out/pv_$v -name "*kernel_stats.csv" | head -1); head -12 "$f2" | cut -d, -f1-4
 done
-cp ab/.inplace.so $L

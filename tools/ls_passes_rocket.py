@@ -37,7 +37,7 @@ for i in range(10):
     sv.iterate(N.MODEL_ROCKET, theta, x0, C, c, nb, 0.2, 5, i, 1e-4, 0.0, 10 ** 9)
     al = sv.alpha.clone()
     hist = {f"{x:g}": int((al == x).sum()) for x in (1.0, 0.2, 0.04, 0.008, 0.0016)}
-    # lane-pair search (today): 32 problems per wave, rounds of 2 candidates
+    # a lane-pair search (removed): 32 problems per wave, rounds of 2 candidates
     w32 = al.view(-1, 32)
     r2 = float((w32 < 0.2 - 1e-7).any(1).float().mean())          # some problem needs candidates 3+
     r3 = float((w32 < 0.008 - 1e-9).any(1).float().mean())        # ... candidate 5

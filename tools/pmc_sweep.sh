@@ -10,6 +10,7 @@ mkdir -p $OUT
 export DILQR_SKIP_BUILD_ID=1
 L=$R/differentiable-ilqr_amd/dilqr/libdilqr.so
 cp $L $OUT/.inplace.so
+trap 'cp "$OUT/.inplace.so" "$L"' EXIT   # restore the in-tree library on any exit
 cd /tmp && export TMPDIR=/tmp
 GROUPS_=("SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY"
          "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS"
@@ -28,8 +29,7 @@ for f in $OUT/.inplace.so $VARIANTS; do
     timeout -k 10 -s KILL 120 rocprofv3 --kernel-trace --pmc $grp -d $OUT/${v}_p$i -o run --output-format csv -- \
         python3 $R/bench.py --kernels-only --profile-set ${PSET:-rocket} > $OUT/${v}_p$i.log 2>&1
     rc=$?; echo "$v pass $i rc=$rc"
-    [ $rc -eq 0 ] || { cp $OUT/.inplace.so $L; exit $rc; }
+    [ $rc -eq 0 ] || exit $rc
   done
 done
-cp $OUT/.inplace.so $L
 echo PMCS_DONE
