@@ -4,6 +4,7 @@
 // Instantiated per model in tu_mpc_<model>.hip.  See DESIGN.md §2, §3, §5.
 #pragma once
 #include "dilqr_common.h"
+#include "dilqr_cost_check.h"
 #include "dilqr_launch.h"
 
 namespace dilqr {
@@ -214,6 +215,58 @@ struct CostDiagConst {
   }
 };
 
+// The whole-solve kernel's speculative cost route (k_mpc_solve_fixed): a wave
+// iterates on the guess "the cost is record 0's diag(q), p at every t" while
+// this state, carried with the lane, tests records 1 .. T-2 of the caller's C, c
+// against the guess under the iterations (SpecSchedule, dilqr_cost_check.h).
+// DILQR_SPEC_SPREAD: the iterations the records are spread over (clamped to the
+// solve's count, which the default means; 0: all of them after the last
+// iteration).  The events ride on the sweep's steps only.  vmcnt counts in
+// issue order, so a trajectory prefetch issued behind a record's loads cannot
+// be consumed before the record has arrived: the sweep consumes its prefetch
+// two steps (~1.1 us) later, which covers a record's latency; the line search
+// consumes its own one step later, which does not (events there measured
+// x0.97, DESIGN.md §3 "round 8").
+#ifndef DILQR_SPEC_SPREAD
+#define DILQR_SPEC_SPREAD (1 << 20)
+#endif
+constexpr int kSpecSpread = DILQR_SPEC_SPREAD;
+// The models whose whole-solve kernel takes the route: the one it was measured
+// on, the headline's (DESIGN.md §3 "round 8").  Every other model keeps the
+// analysing begin.
+template <class Model>
+struct SpecCostRoute : std::false_type {};
+template <>
+struct SpecCostRoute<Cartpole> : std::true_type {};
+
+template <int d>
+struct CostCheck {
+  SpecSchedule sch;
+  const float* __restrict__ C;  // the caller's cost
+  const float* __restrict__ c;
+  unsigned bad;                 // nonzero once a tested record differs from the guess (per lane)
+  float Cb[d][d], cb[d];        // the record in flight
+  DEV void init(const float* __restrict__ C_, const float* __restrict__ c_, int T, int iters) {
+    C = C_; c = c_; bad = 0u;
+    sch.init(T, iters, kSpecSpread, T, blockIdx.x);
+  }
+  // one event: test the buffered record, issue the next one's loads
+  DEV void event(const CostDiagConst<d>& guess, int B, int b) {
+    if (sch.take_fold()) bad |= cost_record_diff(Cb, cb, guess.dg, guess.cc);
+    const int t = sch.take_load();                          // (wave-uniform)
+    if (t) CostFull<d>{C, c}.load(Cb, cb, t, B, b);
+  }
+  // whatever the iterations' steps left: the rest of the records, one by one
+  DEV void drain(const CostDiagConst<d>& guess, int B, int b) {
+    if (sch.take_fold()) bad |= cost_record_diff(Cb, cb, guess.dg, guess.cc);
+    for (int t = sch.take_load(); t; t = sch.take_load()) {
+      CostFull<d>{C, c}.load(Cb, cb, t, B, b);
+      sch.take_fold();
+      bad |= cost_record_diff(Cb, cb, guess.dg, guess.cc);
+    }
+  }
+};
+
 // What a lane of a whole-solve kernel keeps in registers from one phase of its
 // solve to the next (begin -> iteration -> sweep -> line search -> the next
 // iteration), instead of storing it and reading it back a few hundred cycles
@@ -232,6 +285,14 @@ struct LaneCarry {
   // tail of the current trajectory, record T-1: from begin's rollout, then the
   // accepted candidate's at the line search's last step; the next sweep starts on it
   float xl[n], ul[m];
+  // the speculative cost route's verifier (k_mpc_solve_fixed; unused elsewhere)
+  CostCheck<d> chk;
+  // one sweep step of a speculating wave (ilqr_problem SPEC):
+  // called before the step issues its own trajectory prefetch, so the record's
+  // loads are older than the prefetch in vmcnt's issue order
+  DEV void spec_step(int B, int b) {
+    if (chk.sch.tick()) chk.event(cc, B, b);
+  }
 };
 
 // The box bounds as a compile-time mode (DILQR_BOUNDS_*): scalar bounds are
@@ -594,7 +655,8 @@ DEV int line_search(int T, int B, int b, const Model md, const float* __restrict
 // (no load to wait for before its first step; the prefetches of T-2, T-3 are
 // in flight behind it), leaves the head records (u_0, x_1, u_1) of the
 // trajectory in *cy as it passes them, and the line search takes them from there.
-template <class Model, int BM, int TL, bool ROLLOUT, class CostT, bool PREV = false, bool CARRY = false>
+template <class Model, int BM, int TL, bool ROLLOUT, class CostT, bool PREV = false, bool CARRY = false,
+          bool SPEC = false>
 DEV int ilqr_problem(int T, int B, int b, const Model md, const float* __restrict__ x_init, const CostT& cs,
                      float* __restrict__ pack_out, unsigned char* __restrict__ sym_out, const float* __restrict__ x,
                      const float* __restrict__ u, const Bounds& bd, float decay, int max_ls,
@@ -707,6 +769,7 @@ DEV int ilqr_problem(int T, int B, int b, const Model md, const float* __restric
       }
     };
     auto sweep_step = [&](int t, auto last_c) {
+      if constexpr (SPEC) cy->spec_step(B, b);
       if constexpr (kPF >= 2) n2.load(cs, x, u, bd, t > 1 ? t - 2 : 0, B, b);   // prefetch step t-2
       else n1.load(cs, x, u, bd, t > 0 ? t - 1 : 0, B, b);                       // prefetch step t-1
       float g[GREC];
@@ -839,7 +902,7 @@ struct LaneIter {
 };
 
 template <class Model, int BM, bool LG, bool FIRST, bool PREV = true, int GS = kBlock, bool CARRY = false,
-          bool ONLY_DC = false>
+          int ONLY_DC = 0>
 DEV LaneIter mpc_iteration_lane(int T, int B, int b, const Model md, const float* __restrict__ x_init,
                                 const float* __restrict__ C, const float* __restrict__ c, const Bounds& bd,
                                 float decay, int max_ls, const MpcState& S, float* __restrict__ du_sq,
@@ -871,19 +934,21 @@ DEV LaneIter mpc_iteration_lane(int T, int B, int b, const Model md, const float
     // ONLY_DC: the caller has established (wave-uniformly) that every problem of
     // this wave is flagged kCostDiag | kCostTinv, so this instantiation holds no
     // other cost path (and no join with one: a join makes the compiler wait for
-    // whatever any of the paths may have left in flight, trajectory stores included)
-    if (ONLY_DC || (pk & (kCostDiag | kCostTinv)) == (kCostDiag | kCostTinv)) {
+    // whatever any of the paths may have left in flight, trajectory stores included).
+    // ONLY_DC == 2: the same for a wave that only guesses so (the speculative
+    // route): its steps also carry the verifier's events (LaneCarry::spec_step)
+    if (ONLY_DC != 0 || (pk & (kCostDiag | kCostTinv)) == (kCostDiag | kCostTinv)) {
       if constexpr (packed_diag_ok<n + m>()) {
         CostDiagConst<n + m> cc;
         if constexpr (CARRY) cc = cy->cc;                   // begin's pk_first: the record init() reads
         else cc.init(S.Cpk, T, B, b);
-        win = ilqr_problem<Model, BM, TRAJ_REC, true, CostDiagConst<n + m>, PREV, CARRY>(T, B, b, md, x_init, cc, nullptr, nullptr, xcur, nullptr, bd,
+        win = ilqr_problem<Model, BM, TRAJ_REC, true, CostDiagConst<n + m>, PREV, CARRY, ONLY_DC == 2>(T, B, b, md, x_init, cc, nullptr, nullptr, xcur, nullptr, bd,
                                                       decay, max_ls, gr, xsa, nullptr, xsb, nullptr, du_sq, cost,
                                                       alpha, b_lds, prev_cost, nullptr, cy);
       } else {
         __builtin_unreachable();
       }
-    } else if constexpr (ONLY_DC) {
+    } else if constexpr (ONLY_DC != 0) {
       __builtin_unreachable();
     } else if (pk & kCostDiag) {           // set by iteration 0 only when packed_diag_ok
       if constexpr (packed_diag_ok<n + m>())
@@ -1225,18 +1290,20 @@ __global__ void __launch_bounds__(kBlock, DILQR_SOLVE_OCC) k_mpc_solve_fixed(int
   // the lane's carry: x_init, the cost registers, and the head and tail records
   // of its current trajectory stay in registers from here to the last iteration
   LaneCarry<Model> cy;
-  const unsigned pk = S.Cpk ? mpc_begin_lane<Model, true, true>(T, B, b, md, x_init, u_init, S, C, c, &cy)
-                            : mpc_begin_lane<Model, false, true>(T, B, b, md, x_init, u_init, S, nullptr, nullptr, &cy);
-  DILQR_STAMP(1);
+  unsigned pk = 0u;
   LaneIter r{0.f, 0.f, 0};
   int cur = 0, best = 0, best_iter = 0;
   float best_cost = 0.f;
   bool take = true;
   const size_t plane = (size_t)T * m * B;                   // one iteration's du rows
-  // the iterations; only_dc: an instantiation that holds the time-invariant
-  // diagonal cost path alone (mpc_iteration_lane ONLY_DC)
+  // the iterations; only_dc: 1 an instantiation that holds the time-invariant
+  // diagonal cost path alone (mpc_iteration_lane ONLY_DC), 2 that of a wave
+  // which only guesses so and tests the guess as it goes (below)
   auto iterate = [&](auto only_dc) {
-    constexpr bool DC = decltype(only_dc)::value;
+    constexpr int DC = decltype(only_dc)::value;
+    r = LaneIter{0.f, 0.f, 0};
+    best_iter = 0;
+    take = true;
     r = mpc_iteration_lane<Model, BM, LG, false, false, kSolveLpw, true, DC>(T, B, b, md, x_init, C, c, bd, decay,
                                                                              max_ls, S, S.du_sq, lds_gains, 0, 0, pk,
                                                                              0.f, nullptr, &cy);
@@ -1254,17 +1321,82 @@ __global__ void __launch_bounds__(kBlock, DILQR_SOLVE_OCC) k_mpc_solve_fixed(int
       cur = r.slot;
     }
   };
+  // The speculative cost route.  The cost the reference's
+  // callers pass is diag(q), p repeated over t, and for such a problem every
+  // cost register is known from record 0; begin's pass over all T records
+  // (HBM-bound, ~3.5x the rollout's own time) only confirms it.  So a wave
+  // whose problems all LOOK like that — the guard: record 0 has every
+  // off-diagonal word +0.0 and record T-1 equals it bit for bit — runs the
+  // rollout alone, iterates on record 0's registers at once, and reads records
+  // 1 .. T-2 under the iterations' steps, where HBM is idle (CostCheck).
+  // `bad == 0` over all records is exactly flags == 7 of the analysing begin,
+  // and then the wave commits what that begin leaves: the flags and the one
+  // packed record at t = T-1.  Otherwise — wave-uniformly, one ballot after
+  // the last iteration — the wave runs the ordinary sequence from the top,
+  // which rewrites every word the speculative pass wrote (S.slot, slot 0, the
+  // candidates' slots, the du_sq planes, the gain records in LDS) before
+  // reading it, so its lanes end with the bits of a wave that never
+  // speculated.  A wave failing the
+  // guard (a terminal cost, a dense or time-varying one) pays two record reads.
+  // A wrong guess cannot misaddress: every address of an iteration is formed
+  // from b, t, threadIdx and the slot indices free_slots() returns (0..3 for
+  // any cur, best in 0..3, which is all LaneIter::slot can hold); no address
+  // depends on a cost value.  Garbage costs give garbage or non-finite floats,
+  // which the iteration handles as for a non-finite initial state.
+  // The route is compiled only for the instantiation it was measured on
+  // (DESIGN.md §3 "round 8"): cartpole (SpecCostRoute), unconstrained, gain
+  // records in LDS.  The bounded and gains-in-HBM kernels and the other models
+  // keep the analysing begin.
+  constexpr int d = Model::N + m;
+  bool committed = false;
+  if constexpr (BM == DILQR_BOUNDS_NONE && LG && SpecCostRoute<Model>::value && packed_diag_ok<d>()) {
+    bool spec = false;
+    if (S.Cpk) {
+      float C0[d][d], c0[d], Cl[d][d], cl[d];
+      const CostFull<d> full{C, c};
+      full.load(C0, c0, 0, B, b);
+      full.load(Cl, cl, T - 1, B, b);
+#pragma unroll
+      for (int i = 0; i < d; ++i) { cy.cc.dg[i] = C0[i][i]; cy.cc.cc[i] = c0[i]; }
+      const unsigned miss = cost_record_diff(C0, c0, cy.cc.dg, cy.cc.cc) | cost_record_diff(Cl, cl, cy.cc.dg, cy.cc.cc);
+      spec = __ballot(miss != 0u) == 0ull;
+    }
+    if (spec) {
+      mpc_begin_lane<Model, false, true>(T, B, b, md, x_init, u_init, S, nullptr, nullptr, &cy);
+      DILQR_STAMP(1);
+      cy.chk.init(C, c, T, iters);
+      pk = kCostSym | kCostDiag | kCostTinv;
+      iterate(std::integral_constant<int, 2>{});
+      cy.chk.drain(cy.cc, B, b);
+      if (__ballot(cy.chk.bad != 0u) == 0ull) {
+        constexpr int PK = packed_cost_floats<d>();
+        float rec[PK];                                      // pack_cost of record 0: diag, c, zeros
+#pragma unroll
+        for (int k = 0; k < PK; ++k) rec[k] = 0.f;
+#pragma unroll
+        for (int i = 0; i < d; ++i) { rec[i] = cy.cc.dg[i]; rec[d + i] = cy.cc.cc[i]; }
+        SoaRec<PK>::store(S.Cpk, rec, T, T - 1, B, b);
+        S.cost_sym[b] = (unsigned char)pk;
+        committed = true;
+      }
+    }
+  }
   // A wave whose problems all have a time-invariant diagonal cost (the
   // reference's callers' diag(q), p: the common case) runs its iterations in a
   // loop of their own.  The test is wave-uniform (a ballot over the wave's
   // live lanes), so that loop has no join with the other cost paths inside an
   // iteration; in the shared loop those joins drain the lane's trajectory
   // stores at the start and at the end of every iteration.
-  bool wave_dc = false;
-  if constexpr (packed_diag_ok<Model::N + m>())
-    wave_dc = __ballot((pk & (kCostDiag | kCostTinv)) != (kCostDiag | kCostTinv)) == 0ull;
-  if (wave_dc) iterate(std::true_type{});
-  else iterate(std::false_type{});
+  if (!committed) {
+    pk = S.Cpk ? mpc_begin_lane<Model, true, true>(T, B, b, md, x_init, u_init, S, C, c, &cy)
+               : mpc_begin_lane<Model, false, true>(T, B, b, md, x_init, u_init, S, nullptr, nullptr, &cy);
+    DILQR_STAMP(1);
+    bool wave_dc = false;
+    if constexpr (packed_diag_ok<d>())
+      wave_dc = __ballot((pk & (kCostDiag | kCostTinv)) != (kCostDiag | kCostTinv)) == 0ull;
+    if (wave_dc) iterate(std::integral_constant<int, 1>{});
+    else iterate(std::integral_constant<int, 0>{});
+  }
   // the state the per-iteration launches leave behind
   S.cost[b] = r.cost;
   S.alpha[b] = r.alpha;
