@@ -62,6 +62,20 @@ inline bool bad_bounds(const dilqr_bounds& b) {
   return b.mode != DILQR_BOUNDS_NONE && b.mode != DILQR_BOUNDS_SCALAR;
 }
 
+// Run-time launch choices as compile-time constants for a generic lambda f
+// (a bounds mode that is neither NONE nor TENSOR counts as SCALAR)
+template <class F>
+inline void with_bounds_mode(int mode, F&& f) {
+  if (mode == DILQR_BOUNDS_TENSOR) f(std::integral_constant<int, DILQR_BOUNDS_TENSOR>{});
+  else if (mode != DILQR_BOUNDS_NONE) f(std::integral_constant<int, DILQR_BOUNDS_SCALAR>{});
+  else f(std::integral_constant<int, DILQR_BOUNDS_NONE>{});
+}
+template <class F>
+inline void with_flag(bool flag, F&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
+
 // (n, m) shapes compiled for the generic (LinDx / Riccati / adjoint) kernels.
 // Model kernels use their own fixed shapes.
 #define DILQR_FOR_EACH_SHAPE(X) X(3, 1) X(5, 1) X(4, 3) X(4, 1) X(2, 1) X(4, 2) X(6, 2) X(6, 1)

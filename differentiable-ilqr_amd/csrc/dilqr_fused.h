@@ -6,6 +6,7 @@
 #include "dilqr_common.h"
 #include "dilqr_cost_check.h"
 #include "dilqr_launch.h"
+#include "dilqr_stop_rule.h"
 
 namespace dilqr {
 
@@ -68,6 +69,17 @@ DEV void st_xu(float* __restrict__ xp, float* __restrict__ up, const float (&x)[
   } else {
     st(xp + tb * n, x);
     st(up + tb * m, u);
+  }
+}
+
+// problem b's TRAJ_AOS trajectory from (src_x, src_u) to (dst_x, dst_u)
+template <int n, int m>
+DEV void copy_traj_aos(float* dst_x, float* dst_u, const float* src_x, const float* src_u, int T, int B, int b) {
+  for (int t = 0; t < T; ++t) {
+    const size_t tb = (size_t)t * B + b;
+    float xt[n], ut[m];
+    ld(xt, src_x + tb * n); ld(ut, src_u + tb * m);
+    st(dst_x + tb * n, xt); st(dst_u + tb * m, ut);
   }
 }
 
@@ -848,7 +860,7 @@ __global__ void __launch_bounds__(kBlock) k_ilqr_iterate(int T, int B, const flo
                                                    bd, decay,
                                             max_ls, GainRecs{ws, B, b},
                                             x_out, u_out, xb, ub, du_sq, cost, alpha);
-  if (win) {
+  if (win) {                                  // (copy_traj_aos, written out: the call moves this kernel's listing)
     for (int t = 0; t < T; ++t) {
       const size_t tb = (size_t)t * B + b;
       float xt[n], ut[m];
@@ -973,11 +985,6 @@ DEV LaneIter mpc_iteration_lane(int T, int B, int b, const Model md, const float
   return LaneIter{cost, alpha, win ? sb : sa};
 }
 
-// best-iterate test (mpc_explicit.py:277-283): iteration 0 always takes it
-DEV bool mpc_takes_best(bool first, float cost, float best_cost, float best_cost_eps) {
-  return first || cost <= best_cost + best_cost_eps;
-}
-
 // One launch per MPC iteration (the stop-rule path; fixed-count solves of the
 // single-lane models run k_mpc_solve_fixed instead).  FIRST: iteration 0 — its
 // own instantiation, so the steady-state kernel carries no copy-building code
@@ -1021,22 +1028,7 @@ __global__ void __launch_bounds__(kBlock) k_mpc_iterate(int T, int B, const floa
   DILQR_STAMP(7);
 }
 
-// ---------------- the stop rule (mpc_explicit.py:264, 279, 297-299), split so
-// that no launch waits on a grid-wide fan-in:
-//  * k_mpc_norm_rows (after iteration k): full_du_norm with the reference's
-//    batch-mixing rows (the .transpose(1,2).contiguous().view(n_batch,-1) quirk,
-//    lqr_step_explicit.py:245-247), best_du of the problems that took iteration
-//    k, and per-workgroup partials (max row norm, any "improved") into plane
-//    k&1 of the sync area.  Plain stores only.
-//  * mpc_decide, in the prologue of iteration k+1 (every workgroup, redundantly,
-//    identically): reduce the partials of iteration k, apply the stop rule to the
-//    control state S_k -> S_{k+1}; workgroup 0 publishes S_{k+1} in ctrl[(k+1)&1].
-//    The kernel boundary orders everything, so no fences or atomics are needed
-//    (measured: the former last-workgroup fan-in cost 8 of 14 us per iteration).
-// Sync area (uints): [16 + (2*par + 0)*G_MAX + blk] max bits, [16 + (2*par+1)*G_MAX
-// + blk] any, G_MAX = ceil(B/64).
-DEV int sync_gmax(int B) { return (B + 63) / 64; }
-
+// ---------------- the stop rule of the per-iteration launches (dilqr_stop_rule.h)
 // Prologue of iteration k >= 1 (one 64-lane wave per workgroup): the stop rule
 // for iteration k-1.  Returns true when the solve has stopped (the wave exits).
 DEV bool mpc_decide(const MpcState& S, int B, int k, int G, float eps, int not_improved_lim) {
@@ -1087,13 +1079,13 @@ DEV bool mpc_decide(const MpcState& S, int B, int k, int G, float eps, int not_i
   dilqr_mpc_ctrl out = in;
   if (!in.stopped) {
     // wave-uniform decisions by ballot: max < eps <=> every lane's max < eps
-    // (fdn >= 0, so uint order is float order; a NaN fails `< eps` in its lane
-    // as it fails it as the max)
-    const bool all_below = __ballot(!(__uint_as_float(mx) < eps)) == 0ull;
+    // (du_below; a NaN fails `< eps` in its lane as it fails it as the max)
+    const bool all_below = __ballot(!du_below(mx, eps)) == 0ull;
     const bool any_imp = __ballot(any != 0) != 0ull;
     out.iter = in.iter + 1;
-    out.n_not_improved = any_imp ? 0 : in.n_not_improved + 1;     // mpc_explicit.py:264, 279
-    if (all_below || out.n_not_improved > not_improved_lim) out.stopped = 1;   // 297-299
+    const StopState st = stop_rule_step(in.n_not_improved, any_imp, all_below, not_improved_lim);
+    out.n_not_improved = st.n_not_improved;
+    if (st.stopped) out.stopped = 1;
     if (blockIdx.x == 0) {                              // the published max (informational)
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) {
@@ -1416,10 +1408,10 @@ __global__ void __launch_bounds__(kBlock, DILQR_SOLVE_OCC) k_mpc_solve_fixed(int
 // problem in one workgroup those are a barrier and an LDS reduction, so the
 // loop needs no launch per iteration and no host poll.  Each lane runs the
 // same per-lane code as k_mpc_solve_fixed (begin, iteration 0 without PREV,
-// then PREV), and after each iteration the workgroup forms the rows exactly as
-// k_mpc_norm_rows does (same order of summation) and applies the rule exactly
-// as mpc_decide does: the same iterates, costs, best_du, full_du_norm and
-// stop iteration as the per-iteration launches
+// then PREV), and after each iteration the workgroup forms the rows as
+// k_mpc_norm_rows does and applies the rule as mpc_decide does (stop_rule_step,
+// written out below: the call moves this kernel's listing): the same iterates,
+// costs, best_du, full_du_norm and stop iteration as the per-iteration launches
 // (test_small_batch_solve_equals_per_iteration_launches).
 // (256: four waves, one per SIMD of the CU — a larger workgroup would bound the
 // per-lane iteration's registers at 512 / waves-per-SIMD and spill it; the first
@@ -1469,10 +1461,7 @@ __global__ void __launch_bounds__(kSmallMax) k_mpc_solve_small(int T, int B, con
     unsigned mx = 0u;
     int any = 0;
     if (act) {                                             // k_mpc_norm_rows, row b
-      float s2 = 0.f;
-      const float* p = S.du_sq + (size_t)b * TM;
-      for (int i = 0; i < TM; ++i) s2 += p[i];
-      const float fdn = sqrtf(s2);
+      const float fdn = quirk_row_norm(S.du_sq + (size_t)b * TM, TM);
       S.full_du_norm[b] = fdn;
       if (imp) S.best_du[b] = fdn;
       mx = __float_as_uint(fdn);
@@ -1553,45 +1542,33 @@ inline bool lds_gains_fit(size_t lds, int B) {
 // instantiation
 template <class MD>
 int launch_mpc_step_tpp(const MpcStepArgs& a) {
-#define LAUNCH_IT(BM_, LG_, FIRST_, LDS_)                                                                     \
-  k_mpc_iterate<MD, BM_, LG_, FIRST_><<<grid_for(a.B), kBlock, LDS_, a.stream>>>(                            \
-      a.T, a.B, a.theta, a.x_init, a.C, a.c, a.bd, a.decay, a.max_ls, a.iteration, a.best_cost_eps, a.eps, a.lim, \
-      a.G, a.st)
-#define LAUNCH_MPC(BM_)                                                                                      \
-  do {                                                                                                       \
-    const size_t lds = (size_t)a.T * kBlock * (MD::N * MD::M + MD::M) * sizeof(float);                      \
-    const bool lg = lds_gains_fit(lds, a.B);                                                                 \
-    if (a.iteration == 0 && lg) LAUNCH_IT(BM_, true, true, lds);                                             \
-    else if (a.iteration == 0) LAUNCH_IT(BM_, false, true, 0);                                               \
-    else if (lg) LAUNCH_IT(BM_, true, false, lds);                                                           \
-    else LAUNCH_IT(BM_, false, false, 0);                                                                    \
-  } while (0)
-  if (a.bd.mode == DILQR_BOUNDS_TENSOR) LAUNCH_MPC(DILQR_BOUNDS_TENSOR);
-  else if (a.bd.mode != DILQR_BOUNDS_NONE) LAUNCH_MPC(DILQR_BOUNDS_SCALAR);
-  else LAUNCH_MPC(DILQR_BOUNDS_NONE);
-#undef LAUNCH_MPC
-#undef LAUNCH_IT
+  const size_t lds = (size_t)a.T * kBlock * (MD::N * MD::M + MD::M) * sizeof(float);
+  with_bounds_mode(a.bd.mode, [&](auto bm) {
+    with_flag(lds_gains_fit(lds, a.B), [&](auto lg) {
+      with_flag(a.iteration == 0, [&](auto first) {
+        k_mpc_iterate<MD, decltype(bm)::value, decltype(lg)::value, decltype(first)::value>
+            <<<grid_for(a.B), kBlock, decltype(lg)::value ? lds : 0, a.stream>>>(
+                a.T, a.B, a.theta, a.x_init, a.C, a.c, a.bd, a.decay, a.max_ls, a.iteration, a.best_cost_eps, a.eps,
+                a.lim, a.G, a.st);
+      });
+    });
+  });
   return launched();
 }
 
 // a whole fixed-count solve of one thread-per-problem model (k_mpc_solve_fixed)
 template <class MD>
 int launch_mpc_solve_tpp(const MpcSolveArgs& a) {
-#define LAUNCH_SOLVE(BM_)                                                                                    \
-  do {                                                                                                       \
-    const size_t lds = (size_t)a.T * kSolveLpw * (MD::N * MD::M + MD::M) * sizeof(float);                   \
-    const int grid = (int)(((long long)a.B + kSolveLpw - 1) / kSolveLpw);                                   \
-    if (lds_gains_fit(lds * kBlock / kSolveLpw, a.B))                                                       \
-      k_mpc_solve_fixed<MD, BM_, true><<<grid, kBlock, lds, a.stream>>>(                                      \
-          a.T, a.B, a.theta, a.x_init, a.u_init, a.C, a.c, a.bd, a.decay, a.max_ls, a.iters, a.best_cost_eps, a.st); \
-    else                                                                                                     \
-      k_mpc_solve_fixed<MD, BM_, false><<<grid, kBlock, 0, a.stream>>>(                                       \
-          a.T, a.B, a.theta, a.x_init, a.u_init, a.C, a.c, a.bd, a.decay, a.max_ls, a.iters, a.best_cost_eps, a.st); \
-  } while (0)
-  if (a.bd.mode == DILQR_BOUNDS_TENSOR) LAUNCH_SOLVE(DILQR_BOUNDS_TENSOR);
-  else if (a.bd.mode != DILQR_BOUNDS_NONE) LAUNCH_SOLVE(DILQR_BOUNDS_SCALAR);
-  else LAUNCH_SOLVE(DILQR_BOUNDS_NONE);
-#undef LAUNCH_SOLVE
+  const size_t lds = (size_t)a.T * kSolveLpw * (MD::N * MD::M + MD::M) * sizeof(float);
+  const int grid = (int)(((long long)a.B + kSolveLpw - 1) / kSolveLpw);
+  with_bounds_mode(a.bd.mode, [&](auto bm) {
+    with_flag(lds_gains_fit(lds * kBlock / kSolveLpw, a.B), [&](auto lg) {
+      k_mpc_solve_fixed<MD, decltype(bm)::value, decltype(lg)::value>
+          <<<grid, kBlock, decltype(lg)::value ? lds : 0, a.stream>>>(a.T, a.B, a.theta, a.x_init, a.u_init, a.C, a.c,
+                                                                     a.bd, a.decay, a.max_ls, a.iters, a.best_cost_eps,
+                                                                     a.st);
+    });
+  });
   return launched();
 }
 
@@ -1602,35 +1579,24 @@ int launch_mpc_solve_small_tpp(const MpcSolveArgs& a, float eps, int lim) {
   if (a.B > kSmallMax) return DILQR_E_SHAPE;
   const int threads = (a.B + 63) / 64 * 64;
   const size_t lds = (size_t)a.T * 64 * (MD::N * MD::M + MD::M) * sizeof(float);
-  const bool lg = threads == 64 && lds <= 65536;
-#define LAUNCH_SMALL(BM_)                                                                                    \
-  do {                                                                                                       \
-    if (lg)                                                                                                  \
-      k_mpc_solve_small<MD, BM_, true><<<1, threads, lds, a.stream>>>(                                        \
-          a.T, a.B, a.theta, a.x_init, a.u_init, a.C, a.c, a.bd, a.decay, a.max_ls, a.iters, a.best_cost_eps, eps, \
-          lim, a.st);                                                                                        \
-    else                                                                                                     \
-      k_mpc_solve_small<MD, BM_, false><<<1, threads, 0, a.stream>>>(                                         \
-          a.T, a.B, a.theta, a.x_init, a.u_init, a.C, a.c, a.bd, a.decay, a.max_ls, a.iters, a.best_cost_eps, eps, \
-          lim, a.st);                                                                                        \
-  } while (0)
-  if (a.bd.mode == DILQR_BOUNDS_TENSOR) LAUNCH_SMALL(DILQR_BOUNDS_TENSOR);
-  else if (a.bd.mode != DILQR_BOUNDS_NONE) LAUNCH_SMALL(DILQR_BOUNDS_SCALAR);
-  else LAUNCH_SMALL(DILQR_BOUNDS_NONE);
-#undef LAUNCH_SMALL
+  with_bounds_mode(a.bd.mode, [&](auto bm) {
+    with_flag(threads == 64 && lds <= 65536, [&](auto lg) {
+      k_mpc_solve_small<MD, decltype(bm)::value, decltype(lg)::value>
+          <<<1, threads, decltype(lg)::value ? lds : 0, a.stream>>>(a.T, a.B, a.theta, a.x_init, a.u_init, a.C, a.c,
+                                                                   a.bd, a.decay, a.max_ls, a.iters, a.best_cost_eps,
+                                                                   eps, lim, a.st);
+    });
+  });
   return launched();
 }
 
 template <class MD>
 int launch_ilqr_iterate_tpp(const IlqrIterArgs& a) {
-#define LAUNCH_IT(BM_)                                                                                        \
-  k_ilqr_iterate<MD, BM_><<<grid_for(a.B), kBlock, 0, a.stream>>>(a.T, a.B, a.theta, a.x_init, a.C, a.c, a.x, a.u, \
-                                                                   a.bd, a.decay, a.max_ls, a.ws, a.x_out,     \
-                                                                   a.u_out, a.cost, a.du_sq, a.alpha, a.ctrl)
-  if (a.bd.mode == DILQR_BOUNDS_TENSOR) LAUNCH_IT(DILQR_BOUNDS_TENSOR);
-  else if (a.bd.mode != DILQR_BOUNDS_NONE) LAUNCH_IT(DILQR_BOUNDS_SCALAR);
-  else LAUNCH_IT(DILQR_BOUNDS_NONE);
-#undef LAUNCH_IT
+  with_bounds_mode(a.bd.mode, [&](auto bm) {
+    k_ilqr_iterate<MD, decltype(bm)::value><<<grid_for(a.B), kBlock, 0, a.stream>>>(
+        a.T, a.B, a.theta, a.x_init, a.C, a.c, a.x, a.u, a.bd, a.decay, a.max_ls, a.ws, a.x_out, a.u_out, a.cost,
+        a.du_sq, a.alpha, a.ctrl);
+  });
   return launched();
 }
 

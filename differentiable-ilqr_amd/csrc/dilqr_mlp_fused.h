@@ -74,14 +74,7 @@ DEV void mlp_iterate_lane(int T, int B, int b, const Model& md, const float* __r
   const int win = ilqr_problem<Model, BM, TRAJ_AOS, false, CostFull<n + m>, PREV>(
       T, B, b, md, x_init, CostFull<n + m>{C, c}, nullptr, nullptr, x, u, bd, decay, max_ls, GainRecs{ws, B, b},
       x_out, u_out, xb, ub, du_sq, cost, alpha, false, prev_cost);
-  if (win) {
-    for (int t = 0; t < T; ++t) {
-      const size_t tb = (size_t)t * B + b;
-      float xt[n], ut[m];
-      ld(xt, xb + tb * n); ld(ut, ub + tb * m);
-      st(x_out + tb * n, xt); st(u_out + tb * m, ut);
-    }
-  }
+  if (win) copy_traj_aos<n, m>(x_out, u_out, xb, ub, T, B, b);
 }
 
 // cost_out and old_cost may alias (an MPC loop passes its cost buffer as both):
@@ -119,6 +112,8 @@ __global__ void __launch_bounds__(kBlock) k_mlp_ilqr_iterate(int T, int B, MlpAr
 // after every iteration, the last one included.  A second barrier keeps the
 // next iteration's du_sq stores behind every lane's read of its row.  The two
 // trajectory buffers swap every iteration.
+// (The row sum and the best copy are written out here: calling quirk_row_norm
+// or copy_traj_aos moved this kernel's listing.)
 template <class Model, int BM>
 __global__ void __launch_bounds__(kSmallMax) k_mlp_mpc_solve_small(int T, int B, MlpArg a,
                                                                    const float* __restrict__ x_init,
@@ -175,7 +170,7 @@ __global__ void __launch_bounds__(kSmallMax) k_mlp_mpc_solve_small(int T, int B,
     unsigned mx = 0u;
     int any = 0;
     if (act) {                                             // k_mpc_best, problem b
-      float s = 0.f;
+      float s = 0.f;                                       // quirk_row_norm
       const float* p = S.du_sq + (size_t)b * TM;
       for (int i = 0; i < TM; ++i) s += p[i];
       const float fdn = sqrtf(s);
@@ -190,7 +185,7 @@ __global__ void __launch_bounds__(kSmallMax) k_mlp_mpc_solve_small(int T, int B,
         best_cost = cost;
         S.best_cost[b] = cost;
         S.best_du[b] = fdn;
-        for (int t = 0; t < T; ++t) {
+        for (int t = 0; t < T; ++t) {                       // copy_traj_aos
           const size_t tb = (size_t)t * B + b;
           float xt[n], ut[m];
           ld(xt, xo + tb * n); ld(ut, uo + tb * m);
@@ -235,28 +230,16 @@ __global__ void __launch_bounds__(kSmallMax) k_mlp_mpc_solve_small(int T, int B,
 // ---------------------------------------------------------------- launchers
 template <int N_, int M_>
 int launch_mlp_ilqr_iterate(const MlpIterArgs& a, int activation) {
-#define LAUNCH_IT2(MD_, BM_, PREV_)                                                                           \
-  k_mlp_ilqr_iterate<MD_, BM_, PREV_><<<grid_for(a.B), kBlock, 0, a.stream>>>(                                \
-      a.T, a.B, a.mlp, a.x_init, a.C, a.c, a.x, a.u, a.bd, a.decay, a.max_ls, a.ws, a.x_out, a.u_out, a.cost, \
-      a.du_sq, a.alpha, a.old_cost, a.ctrl)
-#define LAUNCH_IT(MD_, BM_)                    \
-  do {                                         \
-    if (a.old_cost) LAUNCH_IT2(MD_, BM_, true); \
-    else LAUNCH_IT2(MD_, BM_, false);          \
-  } while (0)
-#define LAUNCH_MD(MD_)                                                                   \
-  do {                                                                                   \
-    if (a.bd.mode == DILQR_BOUNDS_TENSOR) LAUNCH_IT(MD_, DILQR_BOUNDS_TENSOR);           \
-    else if (a.bd.mode != DILQR_BOUNDS_NONE) LAUNCH_IT(MD_, DILQR_BOUNDS_SCALAR);        \
-    else LAUNCH_IT(MD_, DILQR_BOUNDS_NONE);                                              \
-  } while (0)
-  using Sig = Mlp<N_, M_, DILQR_MLP_SIGMOID>;
-  using Rel = Mlp<N_, M_, DILQR_MLP_RELU>;
-  if (activation == DILQR_MLP_SIGMOID) LAUNCH_MD(Sig);
-  else LAUNCH_MD(Rel);
-#undef LAUNCH_MD
-#undef LAUNCH_IT
-#undef LAUNCH_IT2
+  with_flag(activation == DILQR_MLP_SIGMOID, [&](auto sig) {
+    using MD = Mlp<N_, M_, decltype(sig)::value ? DILQR_MLP_SIGMOID : DILQR_MLP_RELU>;
+    with_bounds_mode(a.bd.mode, [&](auto bm) {
+      with_flag(a.old_cost != nullptr, [&](auto prev) {
+        k_mlp_ilqr_iterate<MD, decltype(bm)::value, decltype(prev)::value><<<grid_for(a.B), kBlock, 0, a.stream>>>(
+            a.T, a.B, a.mlp, a.x_init, a.C, a.c, a.x, a.u, a.bd, a.decay, a.max_ls, a.ws, a.x_out, a.u_out, a.cost,
+            a.du_sq, a.alpha, a.old_cost, a.ctrl);
+      });
+    });
+  });
   return launched();
 }
 
@@ -266,24 +249,16 @@ int launch_mlp_mpc_solve_small(const MlpSolveArgs& a, int activation) {
   if constexpr (!mlp_small_ok(N_, M_)) {
     return DILQR_E_SHAPE;
   } else {
-  const int threads = (a.B + 63) / 64 * 64;
-#define LAUNCH_SMALL(MD_, BM_)                                                                                  \
-  k_mlp_mpc_solve_small<MD_, BM_><<<1, threads, 0, a.stream>>>(a.T, a.B, a.mlp, a.x_init, a.u_init, a.C, a.c,   \
-                                                                 a.bd, a.decay, a.max_ls, a.iters,              \
-                                                                 a.best_cost_eps, a.eps, a.lim, a.S)
-#define LAUNCH_MD(MD_)                                                                   \
-  do {                                                                                   \
-    if (a.bd.mode == DILQR_BOUNDS_TENSOR) LAUNCH_SMALL(MD_, DILQR_BOUNDS_TENSOR);        \
-    else if (a.bd.mode != DILQR_BOUNDS_NONE) LAUNCH_SMALL(MD_, DILQR_BOUNDS_SCALAR);     \
-    else LAUNCH_SMALL(MD_, DILQR_BOUNDS_NONE);                                           \
-  } while (0)
-  using Sig = Mlp<N_, M_, DILQR_MLP_SIGMOID>;
-  using Rel = Mlp<N_, M_, DILQR_MLP_RELU>;
-  if (activation == DILQR_MLP_SIGMOID) LAUNCH_MD(Sig);
-  else LAUNCH_MD(Rel);
-#undef LAUNCH_MD
-#undef LAUNCH_SMALL
-  return launched();
+    const int threads = (a.B + 63) / 64 * 64;
+    with_flag(activation == DILQR_MLP_SIGMOID, [&](auto sig) {
+      using MD = Mlp<N_, M_, decltype(sig)::value ? DILQR_MLP_SIGMOID : DILQR_MLP_RELU>;
+      with_bounds_mode(a.bd.mode, [&](auto bm) {
+        k_mlp_mpc_solve_small<MD, decltype(bm)::value><<<1, threads, 0, a.stream>>>(
+            a.T, a.B, a.mlp, a.x_init, a.u_init, a.C, a.c, a.bd, a.decay, a.max_ls, a.iters, a.best_cost_eps, a.eps,
+            a.lim, a.S);
+      });
+    });
+    return launched();
   }
 }
 

@@ -68,10 +68,7 @@ __global__ void __launch_bounds__(256) k_mpc_norm_rows(int TM, int B, int iterat
   unsigned mx = 0u;
   int any = 0;
   if (r < B) {
-    float s = 0.f;
-    const float* p = STAGE ? sdu + (size_t)threadIdx.x * TM : S.du_sq + (size_t)r * TM;
-    for (int i = 0; i < TM; ++i) s += p[i];
-    float fdn = sqrtf(s);
+    const float fdn = quirk_row_norm(STAGE ? sdu + (size_t)threadIdx.x * TM : S.du_sq + (size_t)r * TM, TM);
     S.full_du_norm[r] = fdn;
     mx = __float_as_uint(fdn);              // fdn >= 0: float order == uint order
     if (imp) S.best_du[r] = fdn;
@@ -100,15 +97,14 @@ __global__ void __launch_bounds__(256) k_mpc_norm_rows(int TM, int B, int iterat
 // own plane of du_sq ([iters,T,m,B]) and records, per problem, the last
 // iteration that took the best-iterate branch (best_iter).  At the end this
 // kernel forms best_du — the quirk row (lqr_step_explicit.py:245-247) of that
-// iteration, summed in the same order as k_mpc_norm_rows, so the same bits —
-// and publishes the iteration count in both control words.
+// iteration — and publishes the iteration count in both control words.
 __global__ void __launch_bounds__(256) k_mpc_fixed_finish(int TM, int B, int iterations, MpcState S) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r < B) {
     const int k = S.best_iter[r];
     const float* p = S.du_sq + ((size_t)k * B + r) * TM;
     const float* q = S.du_sq + ((size_t)(iterations - 1) * B + r) * TM;
-    float s = 0.f, s2 = 0.f;
+    float s = 0.f, s2 = 0.f;                // two quirk_row_norm sums, their loads interleaved
     for (int i = 0; i < TM; ++i) { s += p[i]; s2 += q[i]; }
     S.best_du[r] = sqrtf(s);
     S.full_du_norm[r] = sqrtf(s2);          // the last iteration's rows, as the per-iteration rule leaves it
@@ -164,10 +160,7 @@ __global__ void __launch_bounds__(kBlock) k_mpc_best(int T, int B, int first, fl
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const int TM = T * m;
-  float s = 0.f;
-  const float* p = du_sq + (size_t)b * TM;
-  for (int i = 0; i < TM; ++i) s += p[i];
-  float fdn = sqrtf(s);
+  const float fdn = quirk_row_norm(du_sq + (size_t)b * TM, TM);
   full_du_norm[b] = fdn;
   atomicMax(&ctrl->max_du_bits, __float_as_uint(fdn));
   float cb = cost[b];
@@ -179,12 +172,7 @@ __global__ void __launch_bounds__(kBlock) k_mpc_best(int T, int B, int first, fl
   if (take) {
     best_cost[b] = cb;
     best_du[b] = fdn;
-    for (int t = 0; t < T; ++t) {
-      size_t tb = (size_t)t * B + b;
-      float xt[n], ut[m];
-      ld(xt, x + tb * n); ld(ut, u + tb * m);
-      st(best_x + tb * n, xt); st(best_u + tb * m, ut);
-    }
+    copy_traj_aos<n, m>(best_x, best_u, x, u, T, B, b);
   }
 }
 

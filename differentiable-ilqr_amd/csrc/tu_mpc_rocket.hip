@@ -149,14 +149,11 @@ int launch_mpc_step_rocket(const MpcStepArgs& a) {
 }
 
 int launch_ilqr_iterate_rocket(const IlqrIterArgs& a) {
-  if (a.bd.mode != DILQR_BOUNDS_NONE)
-    k_ilqr_iterate_group<Rocket, GAIN_BOX><<<grid_group(a.B), 64, 0, a.stream>>>(
+  with_flag(a.bd.mode != DILQR_BOUNDS_NONE, [&](auto box) {
+    k_ilqr_iterate_group<Rocket, decltype(box)::value ? GAIN_BOX : GAIN_UNC><<<grid_group(a.B), 64, 0, a.stream>>>(
         a.T, a.B, a.theta, a.x_init, a.C, a.c, a.x, a.u, a.bd, a.decay, a.max_ls, a.ws, a.x_out, a.u_out, a.cost,
         a.du_sq, a.alpha, a.ctrl);
-  else
-    k_ilqr_iterate_group<Rocket, GAIN_UNC><<<grid_group(a.B), 64, 0, a.stream>>>(
-        a.T, a.B, a.theta, a.x_init, a.C, a.c, a.x, a.u, a.bd, a.decay, a.max_ls, a.ws, a.x_out, a.u_out, a.cost,
-        a.du_sq, a.alpha, a.ctrl);
+  });
   return launched();
 }
 

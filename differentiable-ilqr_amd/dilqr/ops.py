@@ -678,6 +678,7 @@ class MPCWorkspace:
     def __init__(self, T, B, n, m, device, packed_cost=True, fused=False):
         """fused: ws also holds the fused iteration's second line-search candidate."""
         dev = device
+        self.dims = (n, m, T, B)
         self.xa = torch.empty(T, B, n, device=dev)
         self.ua = torch.empty(T, B, m, device=dev)
         self.xb = torch.empty(T, B, n, device=dev)
@@ -692,6 +693,19 @@ class MPCWorkspace:
         self.best_cost = torch.empty(B, device=dev)
         self.best_du = torch.empty(B, device=dev)
         self.ctrl = torch.zeros(N.CTRL_INTS, dtype=torch.int32, device=dev)
+
+    def update_best(self, first, best_cost_eps, eps, lim):
+        """Best-iterate bookkeeping and the stop rule for the new iterate (xb, ub)."""
+        N.call("dilqr_mpc_update_best_f32", *self.dims, int(first), float(best_cost_eps), float(eps), lim,
+               *map(N.ptr, (self.xb, self.ub, self.cost, self.du_sq, self.fdn, self.best_x, self.best_u,
+                            self.best_cost, self.best_du, self.ctrl)), N.stream(self.ctrl.device))
+
+    def swap(self):
+        self.xa, self.xb, self.ua, self.ub = self.xb, self.xa, self.ub, self.ua
+
+    def stop_seen(self, i, check_every, lqr_iter):
+        """After iteration i: a poll point at which the rule has fired."""
+        return bool(check_every and (i + 1) % check_every == 0 and i + 1 < lqr_iter and int(self.ctrl[1].item()))
 
 
 class MPCSolve:
@@ -1083,16 +1097,16 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
     route = mlp_solve_route(dyn, B, lqr_iter, u_zero_I, verbose)
     ws = MPCWorkspace(T, B, n, m, dev, fused=route != "unfused")
     s = N.stream(dev)
+    bounds, keep = N.make_bounds(u_lower, u_upper)          # (keep: alive until every launch is queued)
+    lim = _lim(not_improved_lim)
     if route == "small":
         # the whole stop-rule loop in one launch (one workgroup holds the batch)
-        bounds, keep = N.make_bounds(u_lower, u_upper)
         u0 = None if u_init is None else _al16(expand_u_init(u_init, T, B, m, dev).expand(T, B, m).contiguous())
         N.call("dilqr_mlp_mpc_solve_small_f32", n, m, T, B, dyn.mlp.desc, N.ptr(x_init), N.ptr(u0), N.ptr(C),
                N.ptr(c), bounds, float(linesearch_decay), int(max_linesearch_iter), int(lqr_iter),
-               float(best_cost_eps), float(eps), _lim(not_improved_lim), N.ptr(ws.xa), N.ptr(ws.ua), N.ptr(ws.xb),
+               float(best_cost_eps), float(eps), lim, N.ptr(ws.xa), N.ptr(ws.ua), N.ptr(ws.xb),
                N.ptr(ws.ub), N.ptr(ws.ws), N.ptr(ws.cost), N.ptr(ws.alpha), N.ptr(ws.du_sq), N.ptr(ws.fdn),
                N.ptr(ws.best_x), N.ptr(ws.best_u), N.ptr(ws.best_cost), N.ptr(ws.best_du), N.ptr(ws.ctrl), s)
-        del keep
         return ws
     if u_init is None:
         ws.ua.zero_()
@@ -1104,27 +1118,19 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
         # per iteration two library calls on the workspace's own buffers: the
         # fused iteration and the best-iterate / stop rule (both no-ops once the
         # rule fired); the flag is polled as below
-        bounds, keep = N.make_bounds(u_lower, u_upper)
-        lim = _lim(not_improved_lim)
         for i in range(lqr_iter):
             dyn.fused_iterate(x_init, C, c, ws.xa, ws.ua, bounds, linesearch_decay, max_linesearch_iter, ws.ws,
                               ws.xb, ws.ub, ws.cost, ws.du_sq, ws.alpha, old_cost=ws.cost if i > 0 else None,
                               ctrl=ws.ctrl)
-            N.call("dilqr_mpc_update_best_f32", n, m, T, B, int(i == 0), float(best_cost_eps), float(eps), lim,
-                   N.ptr(ws.xb), N.ptr(ws.ub), N.ptr(ws.cost), N.ptr(ws.du_sq), N.ptr(ws.fdn), N.ptr(ws.best_x),
-                   N.ptr(ws.best_u), N.ptr(ws.best_cost), N.ptr(ws.best_du), N.ptr(ws.ctrl), s)
-            ws.xa, ws.xb = ws.xb, ws.xa
-            ws.ua, ws.ub = ws.ub, ws.ua
-            if check_every and (i + 1) % check_every == 0 and i + 1 < lqr_iter and int(ws.ctrl[1].item()):
+            ws.update_best(i == 0, best_cost_eps, eps, lim)
+            ws.swap()
+            if ws.stop_seen(i, check_every, lqr_iter):
                 break
-        del keep
         return ws
     stats = None
     if verbose > 0:                        # the table rows, reduced on the stream (util.print_solve_log)
         stats = torch.zeros(max(lqr_iter, 1), 3, device=dev)
         initial = quad_traj_cost(ws.xa, ws.ua, C, c).mean()
-    bounds, keep = N.make_bounds(u_lower, u_upper)
-    lim = _lim(not_improved_lim)
     ran = 0
     for i in range(lqr_iter):
         Fi, _ = dyn.linearize(ws.xa, ws.ua)
@@ -1135,23 +1141,15 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
         dyn.line_search(x_init, C, c, ws.xa, ws.ua, K, k, bounds, zI, linesearch_decay, max_linesearch_iter,
                         ws.xb, ws.ub, ws.cost, ws.du_sq, ws.alpha,
                         old_cost=ws.cost if i > 0 and dyn.carries_cost else None)
-        N.call("dilqr_mpc_update_best_f32", n, m, T, B, int(i == 0), float(best_cost_eps), float(eps), lim,
-               N.ptr(ws.xb), N.ptr(ws.ub), N.ptr(ws.cost), N.ptr(ws.du_sq), N.ptr(ws.fdn), N.ptr(ws.best_x),
-               N.ptr(ws.best_u), N.ptr(ws.best_cost), N.ptr(ws.best_du), N.ptr(ws.ctrl), s)
+        ws.update_best(i == 0, best_cost_eps, eps, lim)
         if stats is not None:
             stats[i, 0] = ws.best_cost.mean()
             stats[i, 1] = ws.fdn.max()
             stats[i, 2] = ws.alpha.mean()
         ran = i + 1
-        ws.xa, ws.xb = ws.xb, ws.xa
-        ws.ua, ws.ub = ws.ub, ws.ua
-        # once the stop rule fired, k_mpc_best ignores further iterations (the
-        # best iterate, its cost, best_du and the control word stay as they
-        # were), so the loop can run on past the stop: the host polls the flag
-        # only every check_every iterations, like mpc_solve
-        if check_every and (i + 1) % check_every == 0 and i + 1 < lqr_iter and int(ws.ctrl[1].item()):
+        ws.swap()
+        if ws.stop_seen(i, check_every, lqr_iter):
             break
-    del keep
     if stats is not None:
         # k_mpc_control counts the iterations that ran (ctrl[0]) and stops counting
         # once the rule fired (ctrl[1])
