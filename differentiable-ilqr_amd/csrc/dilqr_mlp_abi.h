@@ -1,6 +1,6 @@
 // dilqr_mlp_abi.h — host side of the dilqr_mlp_* and dilqr_mlp2_* entry points,
 // shared by every unit that defines one (tu_mlp.hip, tu_mlp2.hip, tu_mpc_mlp.hip,
-// tu_mlp_implicit.hip, tu_mlp_vjp.hip, tu_mlp2_vjp.hip).  A kind of network is
+// tu_mlp_implicit.hip, tu_mlp2_implicit.hip, tu_mlp_vjp.hip, tu_mlp2_vjp.hip).  A kind of network is
 // described once, by a traits type (OneHidden, TwoHidden): its C descriptor, its
 // kernel-argument form, its device model, the descriptor's checks and the
 // dynamic LDS of a launch.  The dispatch on (n, m, activation) is written once

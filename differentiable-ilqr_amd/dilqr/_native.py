@@ -23,6 +23,7 @@ MODEL_MLP = 5          # a network, described by an Mlp (one hidden layer, the d
 MLP_SIGMOID, MLP_RELU = 0, 1
 MLP_MAX_HIDDEN = 256   # DILQR_MLP_MAX_HIDDEN
 MLP2_VJP_MAX_HIDDEN1 = 128   # DILQR_MLP2_VJP_MAX_HIDDEN1: the first width the two-layer weight gradient takes
+MLP2_IMPLICIT_MAX_HIDDEN1 = 96   # DILQR_MLP2_IMPLICIT_MAX_HIDDEN1: the first width the two-layer implicit backward takes
 # (n, m) the one-lane-per-problem kernels are compiled for (csrc/dilqr_common.h DILQR_FOR_EACH_SHAPE)
 LANE_SHAPES = ((3, 1), (5, 1), (4, 3), (4, 1), (2, 1), (4, 2), (6, 2), (6, 1))
 # (n, m) dilqr_mlp_mpc_solve_small_f32 is compiled for (csrc/dilqr_mlp_fused.h mlp_small_ok)
@@ -127,6 +128,8 @@ SIGNATURES = {
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "dilqr_mlp2_linearize_vjp_f32": ([_i, _i, _i, _i, Mlp2, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
                                       _vp, ctypes.c_size_t, _vp], _i),
+    "dilqr_mlp2_implicit_backward_f32": ([_i, _i, _i, _i, Mlp2, _vp, _vp, _vp, _vp, _vp, _vp, Bounds, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _vp], _i),
 }
 # the entry points that return a size, not a status (SIGNATURES is the list of
 # those that return int or a string, which tests/test_abi.py reads off the header)

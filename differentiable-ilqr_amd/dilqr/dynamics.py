@@ -19,7 +19,10 @@ generic.DEVICE_MLP_DEEP_VJP (off too) is on and the first width is within
 N.MLP2_VJP_MAX_HIDDEN1: then it is a HIP backward as well
 (ops.mlp2_linearize_diff, csrc/tu_mlp2_vjp.hip).  Through mpc_explicit.MPC a
 one-hidden-layer module gets the DiLQR implicit backward on its device model
-(ops.mlp_implicit_step, csrc/tu_mlp_implicit.hip, generic.DEVICE_MLP_IMPLICIT).
+(ops.mlp_implicit_step, csrc/tu_mlp_implicit.hip, generic.DEVICE_MLP_IMPLICIT);
+one with two hidden layers and a first width within N.MLP2_IMPLICIT_MAX_HIDDEN1
+does when generic.DEVICE_MLP_DEEP and generic.DEVICE_MLP_DEEP_IMPLICIT (off by
+default) are on (csrc/tu_mlp2_implicit.hip).
 """
 import torch
 import torch.nn.functional as Fn

@@ -17,7 +17,9 @@ layer, sigmoid or relu; NNDynamics.device_model) goes through the HIP MLP
 kernels, the gradient into its weights included — see DEVICE_MLP and
 DEVICE_MLP_VJP below; with DEVICE_MLP_DEEP (off by default) one with two
 hidden layers does too, and with DEVICE_MLP_DEEP_VJP (off by default) so does
-that gradient (a first width of at most 128; wider ones keep the torch graph).
+that gradient (a first width of at most 128; wider ones keep the torch graph);
+with DEVICE_MLP_DEEP_IMPLICIT (off by default) it trains through
+mpc_explicit.MPC, the DiLQR implicit backward on its device model.
 
 lqr_step_forward is the one regular forward of an LQR step: the LQRStep
 factories (lqr_step.py, lqr_step_explicit.py) call it too.  Whether its line
@@ -95,6 +97,14 @@ DEVICE_MLP_DEEP_VJP = False
 # the linearisation's backward (DEVICE_MLP_VJP, or the torch graph).  Off, or
 # outside that envelope: the refusal final_step has always given.
 DEVICE_MLP_IMPLICIT = True
+# With DEVICE_MLP, DEVICE_MLP_DEEP and DEVICE_MLP_IMPLICIT, the same for a
+# two-hidden-layer module inside the kernel's envelope
+# (ops.Mlp2Model.implicit_ok: a first width of at most
+# N.MLP2_IMPLICIT_MAX_HIDDEN1; csrc/tu_mlp2_implicit.hip): its dF, df reach the
+# six parameters through the linearisation's backward (DEVICE_MLP_DEEP_VJP, or
+# the torch graph).  Off, or outside the envelope: the refusal, as it always has
+# been for such a module.
+DEVICE_MLP_DEEP_IMPLICIT = False
 
 
 def device_mlp(dynamics, like):
@@ -117,10 +127,12 @@ def device_solve_ok(mpc, cost, dx, x_init):
 
 
 def implicit_mlp_ok(mpc, cost, dx, x_init):
-    """The MlpModel when final_step's DiLQR implicit backward can run on device
-    (ops.mlp_implicit_step): DEVICE_MLP_IMPLICIT, a one-hidden-layer device
-    model of the solve's (n, m), a quadratic cost, the ANALYTIC linearisation,
-    no slew-rate penalty, no delta_u, no u_zero_I mask."""
+    """The device model when final_step's DiLQR implicit backward can run on
+    device (ops.mlp_implicit_step): DEVICE_MLP_IMPLICIT, a one-hidden-layer
+    device model of the solve's (n, m) — or, with DEVICE_MLP_DEEP and
+    DEVICE_MLP_DEEP_IMPLICIT, a two-hidden-layer one that is implicit_ok —, a
+    quadratic cost, the ANALYTIC linearisation, no slew-rate penalty, no
+    delta_u, no u_zero_I mask."""
     from .mpc_explicit import GradMethods
     if not (DEVICE_MLP_IMPLICIT and isinstance(cost, QuadCost) and mpc.grad_method == GradMethods.ANALYTIC
             and mpc.slew_rate_penalty is None and mpc.delta_u is None and getattr(mpc, "u_zero_I", None) is None):
@@ -128,7 +140,8 @@ def implicit_mlp_ok(mpc, cost, dx, x_init):
     if getattr(dx, "model_id", None) is not None or not hasattr(dx, "grad_input"):
         return None
     mlp = device_mlp(dx, x_init)
-    if not isinstance(mlp, ops.MlpModel) or (mlp.n, mlp.m) != (mpc.n_state, mpc.n_ctrl):
+    deep = DEVICE_MLP_DEEP_IMPLICIT and isinstance(mlp, ops.Mlp2Model) and mlp.implicit_ok
+    if not (isinstance(mlp, ops.MlpModel) or deep) or (mlp.n, mlp.m) != (mpc.n_state, mpc.n_ctrl):
         return None
     return mlp
 
@@ -533,7 +546,8 @@ def final_step(mpc, x_init, cost, dx, x, u, classic):
     and its backward are HIP kernels, DEVICE_MLP_VJP), then the no-op step whose
     backward is the classic adjoint kernel (classic=True) or the DiLQR implicit
     backward: an env_dx model's, or for a network inside implicit_mlp_ok's
-    envelope the kernel on its device model (DEVICE_MLP_IMPLICIT)."""
+    envelope the kernel on its device model (DEVICE_MLP_IMPLICIT; for two hidden
+    layers DEVICE_MLP_DEEP_IMPLICIT as well)."""
     from .lqr_step import LQRStep as ClassicStep
     from .lqr_step_explicit import LQRStep as ExplicitStep
     T, n, m = mpc.T, mpc.n_state, mpc.n_ctrl

@@ -86,7 +86,9 @@ class Mlp2Model(_NetModel):
     not a subclass of it).  Its weight gradient has its own call
     (mlp2_linearize_vjp, csrc/tu_mlp2_vjp.hip; mlp_linearize_vjp stays the
     one-hidden-layer one) and exists when vjp_ok: a first width of at most
-    N.MLP2_VJP_MAX_HIDDEN1."""
+    N.MLP2_VJP_MAX_HIDDEN1.  The DiLQR implicit backward
+    (mlp_implicit_backward, csrc/tu_mlp2_implicit.hip) takes it when
+    implicit_ok: a first width of at most N.MLP2_IMPLICIT_MAX_HIDDEN1."""
     entry, Desc = "dilqr_mlp2_", N.Mlp2
     width_names, layout = "(H1, H2)", "W1 [H1,n+m], b1 [H1], W2 [H2,H1], b2 [H2], W3 [n,H2], b3 [n]"
 
@@ -94,6 +96,7 @@ class Mlp2Model(_NetModel):
         super().__init__(n, m, activation, passthrough, W1, b1, W2, b2, W3, b3)
         self.H1, self.H2 = self.widths
         self.vjp_ok = self.H1 <= N.MLP2_VJP_MAX_HIDDEN1  # inside the envelope of dilqr_mlp2_linearize_vjp_f32
+        self.implicit_ok = self.H1 <= N.MLP2_IMPLICIT_MAX_HIDDEN1  # ... of dilqr_mlp2_implicit_backward_f32
 
 
 MLP_MODELS = (MlpModel, Mlp2Model)
@@ -403,15 +406,21 @@ def mlp2_linearize_diff(mlp2, params, x, u):
 
 def mlp_implicit_backward(mlp, dl_dx, dl_du, C, c, x, u, u_lower, u_upper, want_dF=True):
     """The DiLQR implicit backward at a solution (x [T,B,n], u [T,B,m]) of a
-    solve on the one-hidden-layer MlpModel with cost C [T,B,d,d], c [T,B,d] and
+    solve on an MlpModel or an Mlp2Model with cost C [T,B,d,d], c [T,B,d] and
     box u_lower / u_upper (None, floats or [T,B,m] tensors), for the loss
     gradients dl_dx, dl_du: the derivative of the iLQR fixed point, curvature of
-    the network included (csrc/tu_mlp_implicit.hip; one launch).  Returns
-    (dx_init [B,n], dC, dc, dF [T-1,B,n,d], df [T-1,B,n]); the gradient into
-    the weights is mlp_linearize_vjp(mlp, x, u, dF, df).  Without want_dF, dF
-    and df are None: not computed, not allocated."""
-    if not isinstance(mlp, MlpModel):
-        raise TypeError("dilqr: mlp_implicit_backward is built for the one-hidden-layer MlpModel only")
+    the network included (csrc/tu_mlp_implicit.hip, csrc/tu_mlp2_implicit.hip;
+    one launch).  Returns (dx_init [B,n], dC, dc, dF [T-1,B,n,d],
+    df [T-1,B,n]); the gradient into the weights is
+    mlp_linearize_vjp(mlp, x, u, dF, df), for a two-hidden-layer model
+    mlp2_linearize_vjp(mlp2, x, u, dF, df).  Without want_dF, dF and df are
+    None: not computed, not allocated.  An Mlp2Model must be implicit_ok
+    (H1 <= N.MLP2_IMPLICIT_MAX_HIDDEN1)."""
+    if not isinstance(mlp, MLP_MODELS):
+        raise TypeError("dilqr: mlp_implicit_backward takes an MlpModel or an Mlp2Model (NNDynamics.device_model)")
+    if not getattr(mlp, "implicit_ok", True):
+        raise ValueError(f"dilqr: mlp_implicit_backward takes H1 <= {N.MLP2_IMPLICIT_MAX_HIDDEN1} for a "
+                         f"two-hidden-layer model; got {mlp.H1}")
     dl_dx, dl_du, C, c, x, u = (_al16(_f32(t)) for t in (dl_dx, dl_du, C, c, x, u))
     if x.ndimension() != 3 or u.ndimension() != 3:
         raise ValueError(f"dilqr: mlp_implicit_backward takes x [T,B,n], u [T,B,m]; got {tuple(x.shape)}, "
@@ -447,7 +456,7 @@ def mlp_implicit_backward(mlp, dl_dx, dl_du, C, c, x, u, u_lower, u_upper, want_
     dF = torch.empty(T - 1, B, n, d, device=dev) if want else None
     df = torch.empty(T - 1, B, n, device=dev) if want else None
     if B > 0:                                       # an empty batch: empty outputs, nothing launched
-        N.call("dilqr_mlp_implicit_backward_f32", n, m, T, B, mlp.desc, N.ptr(C), N.ptr(c), N.ptr(x), N.ptr(u),
+        N.call(mlp.entry + "implicit_backward_f32", n, m, T, B, mlp.desc, N.ptr(C), N.ptr(c), N.ptr(x), N.ptr(u),
                N.ptr(dl_dx), N.ptr(dl_du), bounds, N.ptr(ws), N.ptr(dx0), N.ptr(dC), N.ptr(dc), N.ptr(dF),
                N.ptr(df), N.stream(dev))
     del keep

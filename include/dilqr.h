@@ -667,6 +667,34 @@ int dilqr_mlp2_linearize_vjp_f32(int n, int m, int T, int B, dilqr_mlp2 mlp, con
                                  float* dW3, float* db3, int max_waves, void* ws,
                                  size_t ws_bytes, void* stream);
 
+/* ---- DiLQR implicit backward with the two-layer network as the dynamics ----- */
+/* dilqr_mlp_implicit_backward_f32 for a solve whose dynamics are the
+   two-hidden-layer network: the same y, w, dlam and outputs (dx_init, dC, dc,
+   dF, df; dF and df may both be NULL), the same three passes, the same
+   workspace (T*B*dilqr_mlp_implicit_ws_floats(n, m) floats) and the same
+   T = 1 case.  Only F_t and M_t are the network's own: with z1 = W1 tau + b1,
+   z2 = W2 act(z1) + b2, g = act'(z), c = act''(z) = a(1-a)(1-2a) for sigmoid
+   and 0 for relu, both formed from the activation,
+     P   = W2 diag(g1) W1,   s = W3^T lam_{t+1},   v = W2^T (s o g2),
+     F_t = W3 diag(g2) P (+ I on the state block),
+     M_t = P^T diag(s o c2) P + W1^T diag(v o c1) W1;  M_{T-1} = 0; relu: M = 0;
+           the passthrough adds nothing.
+   The gradient into the weights is dilqr_mlp2_linearize_vjp_f32 applied to
+   (dF, df).  A launch keeps the first layer's activations (256 n_hidden1
+   bytes) and one region for v (sigmoid, as many) and the staging area of its
+   records (256 (n+m)^2 bytes) in LDS; n_hidden1 <=
+   DILQR_MLP2_IMPLICIT_MAX_HIDDEN1 keeps that within 48 KiB for every (n, m).
+   n_hidden2 <= DILQR_MLP_MAX_HIDDEN.
+   Errors as dilqr_mlp_implicit_backward_f32, in its order and all before any
+   launch (the descriptor's as dilqr_mlp2_linearize_f32), plus DILQR_E_SHAPE for
+   n_hidden1 above the constant; B = 0 launches nothing. */
+#define DILQR_MLP2_IMPLICIT_MAX_HIDDEN1 96
+int dilqr_mlp2_implicit_backward_f32(int n, int m, int T, int B, dilqr_mlp2 mlp, const float* C,
+                                     const float* c, const float* x, const float* u,
+                                     const float* dl_dx, const float* dl_du,
+                                     dilqr_bounds bounds, float* ws, float* dx_init, float* dC,
+                                     float* dc, float* dF, float* df, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

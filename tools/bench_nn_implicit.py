@@ -17,6 +17,10 @@ package of another checkout (the parent commit, with its own built library):
 the comparison point.  Per batch and arm: one warm-up, then --runs timed runs
 (3); median, min and max.  After each batch ops.mlp_implicit_backward is timed
 by itself, with its bytes and FLOP per (t, b).
+
+--hidden H1,H2 times a two-hidden-layer network (csrc/tu_mlp2_implicit.hip):
+the worker turns generic.DEVICE_MLP_DEEP, DEVICE_MLP_DEEP_VJP and
+DEVICE_MLP_DEEP_IMPLICIT on (they ship off), for both arms.
 """
 import argparse
 import json
@@ -42,7 +46,12 @@ def worker(args):
     assert os.path.realpath(generic.__file__).startswith(os.path.realpath(args.pkg)), generic.__file__
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    dx = NNDynamics(N_STATE, N_CTRL, hidden_sizes=[HIDDEN], activation="sigmoid").to(dev)
+    hidden = [int(h) for h in args.hidden.split(",")]
+    if len(hidden) == 2:
+        generic.DEVICE_MLP_DEEP = generic.DEVICE_MLP_DEEP_VJP = generic.DEVICE_MLP_DEEP_IMPLICIT = True
+    elif len(hidden) != 1:
+        sys.exit("bench_nn_implicit: --hidden takes one width or two")
+    dx = NNDynamics(N_STATE, N_CTRL, hidden_sizes=hidden, activation="sigmoid").to(dev)
     params = list(dx.parameters())
     arms = ["implicit", "classic"] if hasattr(generic, "DEVICE_MLP_IMPLICIT") else ["classic"]
     mid = {}
@@ -100,8 +109,8 @@ def kernel_alone(B, dx, dev, x0, C, c, wx, wu):
     """ops.mlp_implicit_backward by itself (allocations + the one launch), with and without dF, df."""
     import torch
     from dilqr import ops
-    md = dx.device_model(torch.zeros(1, device=dev))
-    n, m, d, H = N_STATE, N_CTRL, N_STATE + N_CTRL, md.H
+    md = dx.device_model(torch.zeros(1, device=dev), deep=True)
+    n, m, d = N_STATE, N_CTRL, N_STATE + N_CTRL
     g = torch.Generator().manual_seed(5)
     u = torch.randn(T, B, m, generator=g).clamp(-1, 1).to(dev)
     x = ops.mlp_rollout(md, x0, u)
@@ -122,7 +131,16 @@ def kernel_alone(B, dx, dev, x0, C, c, wx, wu):
         # (B: z 2d, J 2nd + n, p 2n, M d(d+1) + d; C: z 2d, J 2nd + n; D: z 2d, J 2nd + n, p 2n, My 4d + 1; an
         # activation as 8), the Riccati step (about 2(2 d n^2 + d^2 n) + 4 n^2 m + 2 n m^2) and the outer products
         byts = 4 * (2 * (d * d + d) + 3 * d + 2 * n + m + 2 * (G + d) + d * d + d + (n * d + n if want else 0))
-        walk = H * ((2 * d + 2 * n * d + n + 8) * 3 + 2 * (2 * n) + d * (d + 1) + d + 4 * d + 1)
+        if len(md.widths) == 1:
+            H, = md.widths
+            walk = H * ((2 * d + 2 * n * d + n + 8) * 3 + 2 * (2 * n) + d * (d + 1) + d + 4 * d + 1)
+        else:
+            # two layers: a Jacobian walk is layer 1 (2d + 8 per unit), z2 and the tangent P (3 + 2d per pair of
+            # units), a2 and J (8 + n (1 + 2d) per layer-2 unit); the two walks with M add s (2n), the first term
+            # (d(d+1) + d in B, 4d + 1 in D) per layer-2 unit, v (2 per pair) and the second term per layer-1 unit
+            H1, H2 = md.widths
+            jac = H1 * (2 * d + 8) + H2 * H1 * (3 + 2 * d) + H2 * (8 + n * (1 + 2 * d))
+            walk = 3 * jac + 2 * (2 * n * H2 + 2 * H2 * H1) + (H1 + H2) * (d * (d + 1) + d + 4 * d + 1) + 8 * H1
         ricc = 2 * (2 * d * n * n + d * d * n) + 4 * n * n * m + 2 * n * m * m
         flops = walk + ricc + 3 * d * d + (3 * n * d if want else 0) + 6 * n * d
         t = statistics.median(ts) * 1e-3
@@ -133,7 +151,7 @@ def kernel_alone(B, dx, dev, x0, C, c, wx, wu):
 
 def spawn(pkg, args):
     cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--pkg", pkg, "--batches", args.batches,
-           "--runs", str(args.runs)]
+           "--runs", str(args.runs), "--hidden", args.hidden]
     env = {k: v for k, v in os.environ.items() if k != "DILQR_LIB"}         # each tree loads its own library
     out = subprocess.run(cmd, capture_output=True, text=True, env=env)
     if out.returncode != 0:
@@ -147,6 +165,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="32,4096,65536")
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--hidden", default=str(HIDDEN), help="the hidden width, or H1,H2 for two hidden layers")
     ap.add_argument("--parent", default=None, help="a checkout of the parent commit with its library built")
     ap.add_argument("--out", default=None)
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
@@ -169,7 +188,7 @@ def main():
                             f"{max(s):11.3f} {statistics.median(t):11.3f} {min(t):11.3f} {max(t):11.3f}")
     lines = ["# bench_nn_implicit: one training step, dilqr.MPC (DiLQR implicit backward) against dilqr.mpc.MPC "
              "(classic adjoint)",
-             f"# NNDynamics({N_STATE},{N_CTRL},[{HIDDEN}],sigmoid) T={T} lqr_iter={LQR_ITER} fixed-count, u in [-1,1], "
+             f"# NNDynamics({N_STATE},{N_CTRL},[{args.hidden}],sigmoid) T={T} lqr_iter={LQR_ITER} fixed-count, u in [-1,1], "
              f"dense SPD cost; MPC.forward with gradients + backward; device events; step = the whole of it, tail = "
              f"from the entry of final_step; {args.runs} runs per arm, alternating; ms",
              f"# {device}",
