@@ -1,8 +1,10 @@
 // dilqr_model_kernels.h — the per-row model kernels (dynamics, Jacobian,
 // rollout, linearisation), templated on a Model that provides load(),
 // forward() and jacobian().  Shared by the units that instantiate them:
-// tu_models.hip (the env_dx models, theta a parameter vector) and tu_mlp.hip
-// (the one-hidden-layer network, a by-value descriptor, dilqr_mlp.h).
+// tu_models.hip (the env_dx models, theta a parameter vector), tu_mlp.hip and
+// tu_mlp2.hip (the networks, a by-value descriptor, dilqr_mlp.h, dilqr_mlp2.h)
+// and tu_mlp_slew.hip / tu_mlp2_slew.hip (the networks under the slew-rate
+// augmentation, dilqr_ctrl_through.h).
 #pragma once
 #include "dilqr_common.h"
 

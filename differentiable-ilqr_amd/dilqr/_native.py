@@ -131,6 +131,10 @@ SIGNATURES = {
     "dilqr_mlp2_implicit_backward_f32": ([_i, _i, _i, _i, Mlp2, _vp, _vp, _vp, _vp, _vp, _vp, Bounds, _vp, _vp, _vp,
                                           _vp, _vp, _vp, _vp], _i),
 }
+# the slew-rate augmentation's entry points (csrc/tu_mlp_slew.hip, csrc/tu_mlp2_slew.hip):
+# the argument lists of the plain rollout, linearisation and line search
+SIGNATURES.update({f"dilqr_{kind}_slew_{call}_f32": SIGNATURES[f"dilqr_{kind}_{call}_f32"]
+                   for kind in ("mlp", "mlp2") for call in ("rollout", "linearize", "lqr_forward")})
 # the entry points that return a size, not a status (SIGNATURES is the list of
 # those that return int or a string, which tests/test_abi.py reads off the header)
 SIZE_SIGNATURES = {

@@ -22,7 +22,12 @@ one-hidden-layer module gets the DiLQR implicit backward on its device model
 (ops.mlp_implicit_step, csrc/tu_mlp_implicit.hip, generic.DEVICE_MLP_IMPLICIT);
 one with two hidden layers and a first width within N.MLP2_IMPLICIT_MAX_HIDDEN1
 does when generic.DEVICE_MLP_DEEP and generic.DEVICE_MLP_DEEP_IMPLICIT (off by
-default) are on (csrc/tu_mlp2_implicit.hip).
+default) are on (csrc/tu_mlp2_implicit.hip).  A solve with a slew-rate penalty
+wraps the module in CtrlPassthroughDynamics (below); with
+generic.DEVICE_MLP_SLEW (off by default) that wrapper is a HIP model over the
+device model (csrc/dilqr_ctrl_through.h, ops.slew_dynamics) and the solve stays
+on device, and with generic.DEVICE_MLP_DELTA_U (off too) so does one with
+delta_u.
 """
 import torch
 import torch.nn.functional as Fn

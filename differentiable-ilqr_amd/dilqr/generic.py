@@ -5,7 +5,9 @@ torch Module (e.g. the reference's NNDynamics, dynamics.py:15-130), the
 GradMethods.AUTO_DIFF / FINITE_DIFF linearisations (mpc_explicit.py:547-627),
 non-quadratic costs expanded by autograd (approximate_cost, 468-508), the
 slew-rate augmentation with CtrlPassthroughDynamics (383-466, dynamics.py:
-133-156) and the delta_u trust region (lqr_step_explicit.py:202-215) — runs
+133-156) and the delta_u trust region (lqr_step_explicit.py:202-215; for a
+network with a device model these two have a device route behind
+DEVICE_MLP_SLEW / DEVICE_MLP_DELTA_U, off by default) — runs
 here: the user's Module is evaluated by torch on the GPU, batched over the
 whole horizon wherever the reference loops over t, and every Riccati sweep
 (+pnqp) is the HIP kernel (ops.lqr_backward, c_back fused).  The line search
@@ -19,7 +21,9 @@ DEVICE_MLP_VJP below; with DEVICE_MLP_DEEP (off by default) one with two
 hidden layers does too, and with DEVICE_MLP_DEEP_VJP (off by default) so does
 that gradient (a first width of at most 128; wider ones keep the torch graph);
 with DEVICE_MLP_DEEP_IMPLICIT (off by default) it trains through
-mpc_explicit.MPC, the DiLQR implicit backward on its device model.
+mpc_explicit.MPC, the DiLQR implicit backward on its device model.  With
+DEVICE_MLP_SLEW / DEVICE_MLP_DELTA_U (off by default) a solve of such a network
+with a slew-rate penalty or with delta_u stays on device too.
 
 lqr_step_forward is the one regular forward of an LQR step: the LQRStep
 factories (lqr_step.py, lqr_step_explicit.py) call it too.  Whether its line
@@ -105,6 +109,24 @@ DEVICE_MLP_IMPLICIT = True
 # the torch graph).  Off, or outside the envelope: the refusal, as it always has
 # been for such a module.
 DEVICE_MLP_DEEP_IMPLICIT = False
+# With DEVICE_MLP (and DEVICE_MLP_DEEP for two hidden layers), a solve with a
+# slew-rate penalty that is otherwise inside device_solve_ok's envelope (a
+# quadratic cost, ANALYTIC, no delta_u, not verbose) runs on device as the plain
+# solve of the augmented system (ops.slew_problem, ops.mpc_solve_unfused on
+# ops.slew_dynamics: the reference's CtrlPassthroughDynamics as a HIP model,
+# csrc/dilqr_ctrl_through.h), when the augmented (n + m, m) is a shape the
+# kernels are compiled for.  The gradient is unchanged: final_step's
+# differentiable linearisation of the network, slew_augment, the classic
+# adjoint.  Off: the torch loop, as it always has been.
+DEVICE_MLP_SLEW = False
+# With DEVICE_MLP (and DEVICE_MLP_DEEP), a solve with delta_u and no slew-rate
+# penalty, otherwise inside device_solve_ok's envelope, runs on device
+# (ops.mpc_solve_unfused(delta_u=...): the trust region as per-iteration tensor
+# bounds of the sweep and the line search), and one LQR step with delta_u takes
+# the device line search on the network as it does on an env_dx model
+# (line_search_dynamics).  Off: the torch loop / torch line search.  Both
+# options at once stay in torch whatever the switches say.
+DEVICE_MLP_DELTA_U = False
 
 
 def device_mlp(dynamics, like):
@@ -124,6 +146,27 @@ def device_solve_ok(mpc, cost, dx, x_init):
             and mpc.slew_rate_penalty is None and mpc.delta_u is None and getattr(mpc, "verbose", 0) <= 0):
         return None
     return device_mlp(dx, x_init)
+
+
+def device_option_solve_ok(mpc, cost, dx, x_init):
+    """("slew", handle) or ("delta_u", handle) when the whole solve of an MPC
+    with exactly one of the two options can run on device — device_solve_ok's
+    envelope otherwise, the option's switch on (DEVICE_MLP_SLEW,
+    DEVICE_MLP_DELTA_U), a device model of the solve's (n, m) and, for the
+    slew-rate penalty, an augmented shape the kernels are compiled for; the
+    handle is the ops.Dynamics the solve runs on.  None otherwise."""
+    from .mpc_explicit import GradMethods
+    slew, trust = mpc.slew_rate_penalty is not None, mpc.delta_u is not None
+    if slew == trust or not (DEVICE_MLP_SLEW if slew else DEVICE_MLP_DELTA_U):
+        return None
+    if not (isinstance(cost, QuadCost) and mpc.grad_method == GradMethods.ANALYTIC
+            and getattr(mpc, "verbose", 0) <= 0):
+        return None
+    mlp = device_mlp(dx, x_init)
+    if mlp is None or (mlp.n, mlp.m) != (mpc.n_state, mpc.n_ctrl):
+        return None
+    dyn = ops.slew_dynamics(mlp) if slew else ops.Dynamics(mlp, mlp.n, mlp.m)
+    return None if dyn is None else ("slew" if slew else "delta_u", dyn)
 
 
 def implicit_mlp_ok(mpc, cost, dx, x_init):
@@ -336,10 +379,10 @@ def line_search_dynamics(true_cost, true_dynamics, x, delta_u, env_models):
         factories only; the generic MPC loop has always run them in torch, its
         own use of them being delta_u, the slew-rate penalty and the autograd /
         finite-difference linearisations) -> device, with any delta_u;
-      * a dynamics Module with a device model (DEVICE_MLP) -> device only without
-        delta_u and with the full [T,B,d,d] / [T,B,d] QuadCost.  delta_u is left
-        out because that combination was not built or tested on the MLP entry
-        point, not because the kernel cannot clamp to per-step tensor bounds;
+      * a dynamics Module with a device model (DEVICE_MLP) -> device with the
+        full [T,B,d,d] / [T,B,d] QuadCost, and with delta_u only when
+        DEVICE_MLP_DELTA_U says so (the caller then clamps the rollout to
+        ops.delta_u_rollout_bounds, as for the env_dx models);
       * any other Module -> torch."""
     if not isinstance(true_cost, QuadCost):
         return None
@@ -348,7 +391,7 @@ def line_search_dynamics(true_cost, true_dynamics, x, delta_u, env_models):
         return dyn
     T, B, d = x.shape[0], x.shape[1], dyn.n + dyn.m
     full = tuple(true_cost.C.shape) == (T, B, d, d) and tuple(true_cost.c.shape) == (T, B, d)
-    return dyn if delta_u is None and full else None
+    return dyn if (delta_u is None or DEVICE_MLP_DELTA_U) and full else None
 
 
 def lqr_step_forward(T, n, m, x_init, C, c, F, x, u, true_cost, true_dynamics, u_lower, u_upper, delta_u,
@@ -425,35 +468,19 @@ def slew_augment(mpc, x_init, C, c, F, f, cost, dynamics, x, u):
     T, n, m = mpc.T, mpc.n_state, mpc.n_ctrl
     B = C.size(1)
     nsc = n + m
-    _nsc = nsc + m
     dev, dt = C.device, C.dtype
-    _C = torch.zeros(T, B, _nsc, _nsc, device=dev, dtype=dt)
-    half_gamI = mpc.slew_rate_penalty * torch.eye(m, device=dev, dtype=dt).expand(T, B, m, m)
-    _C[:, :, :m, :m] = half_gamI
-    _C[:, :, -m:, :m] = -half_gamI
-    _C[:, :, :m, -m:] = -half_gamI
-    _C[:, :, -m:, -m:] = half_gamI
-    slew_C = _C.clone()
-    _C = _C + torch.nn.functional.pad(C, (m, 0, m, 0))
-    _c = torch.cat((torch.zeros(T, B, m, device=dev, dtype=dt), c), 2)
+    _x_init, _C, _c = ops.slew_problem(x_init, C, c, mpc.slew_rate_penalty, mpc.prev_ctrl, m)
     _F0 = torch.cat((torch.zeros(m, n + m, device=dev, dtype=dt), torch.eye(m, device=dev, dtype=dt)), 1)
     _F0 = _F0.expand(T - 1, B, m, nsc + m)
     _F1 = torch.cat((torch.zeros(T - 1, B, n, m, device=dev, dtype=dt), F), 3)
     _F = torch.cat((_F0, _F1), 2)
     _f = None if f is None else torch.cat((torch.zeros(T - 1, B, m, device=dev, dtype=dt), f), 2)
-    if mpc.prev_ctrl is not None:
-        prev_u = mpc.prev_ctrl.detach()
-        if prev_u.ndimension() == 1:
-            prev_u = prev_u.unsqueeze(0)
-        if prev_u.ndimension() == 2:
-            prev_u = prev_u.unsqueeze(0)
-    else:
-        prev_u = torch.zeros(1, B, m, device=dev, dtype=dt)
+    prev_u = ops.slew_prev_ctrl(mpc.prev_ctrl, B, m, dev, dt)
     utm1s = torch.cat((prev_u.expand(1, B, m), u.detach()[:-1]))
     _x = torch.cat((utm1s, x), 2)
-    _x_init = torch.cat((prev_u[0].expand(B, m), x_init), 1)
     _dyn = None if isinstance(dynamics, LinDx) else CtrlPassthroughDynamics(dynamics)
-    _cost = QuadCost(_C, _c) if isinstance(cost, QuadCost) else SlewRateCost(cost, slew_C, n, m)
+    _cost = QuadCost(_C, _c) if isinstance(cost, QuadCost) else SlewRateCost(
+        cost, ops.slew_cost_block(T, B, n, m, mpc.slew_rate_penalty, dev, dt), n, m)
     return _x_init, _C, _c, _F, _f, _dyn, _cost, _x
 
 
@@ -491,6 +518,21 @@ def solve(mpc, x_init, cost, dx, n_batch):
                 mlp, None, x_init.detach(), cost.C.detach().contiguous(), cost.c.detach().contiguous(), T,
                 u_zero_I=getattr(mpc, "u_zero_I", None), **MPC.solver_args(mpc))
         return ws.best_x, ws.best_u, ws.best_cost, ws.best_du
+    option = device_option_solve_ok(mpc, cost, dx, x_init)
+    if option is not None:
+        # one of the two options on device: the slew-rate penalty as the plain
+        # solve of the augmented system on the control-passthrough model, or
+        # delta_u as per-iteration tensor bounds; four launches per iteration
+        from .mpc_explicit import MPC
+        which, dyn = option
+        x0, C, c = x_init.detach(), cost.C.detach().contiguous(), cost.c.detach().contiguous()
+        with torch.no_grad():
+            if which == "slew":
+                x0, C, c = ops.slew_problem(x0, C, c, mpc.slew_rate_penalty, mpc.prev_ctrl, m)
+            ws = ops.mpc_solve_unfused(dyn, None, x0.contiguous(), C, c, T, u_zero_I=getattr(mpc, "u_zero_I", None),
+                                       delta_u=mpc.delta_u, **MPC.solver_args(mpc))
+        best_x = ws.best_x[:, :, m:] if which == "slew" else ws.best_x
+        return best_x, ws.best_u, ws.best_cost, ws.best_du
     if mpc.u_init is None:
         u = torch.zeros(T, n_batch, m, device=dev, dtype=x_init.dtype)
     else:

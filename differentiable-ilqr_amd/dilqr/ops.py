@@ -7,7 +7,10 @@ handle (model id, (n, m), and theta / F, f / the MLP descriptor), made by
 device_dynamics from a dynamics object or by Dynamics.of from the public
 functions' (model_id, theta, F, f).  Its three launches (rollout, linearise,
 line search) are the only call sites of those entry points; rollout,
-linearize, mlp_*, lqr_forward and mpc_solve_unfused all go through them.
+linearize, mlp_*, lqr_forward and mpc_solve_unfused all go through them.  A
+network under MPC's slew-rate penalty is one more handle (slew_dynamics: the
+control-passthrough model over the network, its own family of entry points),
+with slew_problem building the augmented problem it solves.
 
 A network is an MlpModel (one hidden layer) or an Mlp2Model (two).  Both take
 their validation from _NetModel and differ in what a kind declares: the prefix
@@ -110,20 +113,23 @@ class Dynamics:
     of the caller, who has validated their shapes; T and B come from the
     buffers."""
 
-    def __init__(self, model_id, n, m, theta=None, F=None, f=None):
+    def __init__(self, model_id, n, m, theta=None, F=None, f=None, slew=False):
+        """slew: the network under the slew-rate augmentation (slew_dynamics):
+        n is the augmented state's, the network's n + m."""
         self.mlp = None
         if isinstance(model_id, MLP_MODELS):
             model_id, theta = N.MODEL_MLP, model_id
         if model_id == N.MODEL_MLP:
             if not isinstance(theta, MLP_MODELS):
                 raise TypeError("dilqr: MODEL_MLP needs an MlpModel or Mlp2Model (NNDynamics.device_model) as theta")
-            if (theta.n, theta.m) != (n, m):        # the kernels index the weights by n and m
+            if (theta.n + (theta.m if slew else 0), theta.m) != (n, m):   # the kernels index the weights by n and m
                 raise ValueError(f"dilqr: MLP model is (n, m) = {(theta.n, theta.m)}; got (n, m) = {(n, m)}")
             self.mlp, theta, F, f = theta, None, None, None
+        self.slew = bool(slew) and self.mlp is not None
         self.model_id, self.n, self.m = model_id, n, m
         self.theta, self.F, self.f = theta, _f32(F), _f32(f)
         # the family of entry points the three launches call
-        self._entry = "dilqr_" if self.mlp is None else self.mlp.entry
+        self._entry = "dilqr_" if self.mlp is None else self.mlp.entry + ("slew_" if self.slew else "")
         # these line searches take the previous one's cost of the accepted
         # candidate as the old cost (as the fused MPC kernel does); the others
         # recompute it
@@ -142,8 +148,20 @@ class Dynamics:
 
     def _head(self, T, B):
         if self.mlp is not None:
-            return self.n, self.m, T, B, self.mlp.desc
+            return self.mlp.n, self.mlp.m, T, B, self.mlp.desc     # the network's own (n, m), under slew too
         return self.model_id, self.n, self.m, T, B, N.ptr(self.theta), N.ptr(self.F), N.ptr(self.f)
+
+    def check(self, x, u):
+        """x [..., n], u [..., m] of a network's handle on the weights' device
+        (the kernels index rows by n and m): the model's own check, under the
+        slew-rate augmentation at the augmented width."""
+        if not self.slew:
+            return self.mlp.check(x, u)
+        if x.shape[-1] != self.n or u.shape[-1] != self.m or x.shape[:-1] != u.shape[:-1]:
+            raise ValueError(f"dilqr: MLP model under the slew-rate augmentation is (n, m) = {(self.n, self.m)}; "
+                             f"got x {tuple(x.shape)}, u {tuple(u.shape)}")
+        if x.device != self.mlp.device or u.device != self.mlp.device:
+            raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
 
     def rollout(self, x_init, u, x_out):
         """util.get_traj (util.py:104-127): x_out [T,B,n] from x_init and u [T,B,m]."""
@@ -162,8 +180,8 @@ class Dynamics:
             N.call("dilqr_linearize_f32", self.model_id, T, B, N.ptr(self.theta), N.ptr(x), N.ptr(u), N.ptr(F),
                    N.ptr(f), N.stream(x.device))
         elif T > 1 and B > 0:                       # the MLP entry point is not handed empty outputs
-            N.call(self._entry + "linearize_f32", self.n, self.m, T, B, self.mlp.desc, N.ptr(x), N.ptr(u), N.ptr(F),
-                   N.ptr(f), N.stream(x.device))
+            N.call(self._entry + "linearize_f32", *self._head(T, B), N.ptr(x), N.ptr(u), N.ptr(F), N.ptr(f),
+                   N.stream(x.device))
         return F, f
 
     def linearize_vjp(self, x, u, gF, gf, *grads, max_waves=0):
@@ -226,6 +244,67 @@ def device_dynamics(dx, like, env=True, mlp=True, deep=False):
         return None
     md = make(like, deep=True) if deep else make(like)
     return None if md is None else Dynamics(md, md.n, md.m)
+
+
+def slew_dynamics(mlp):
+    """The Dynamics handle of the network mlp (an MlpModel or an Mlp2Model)
+    under the slew-rate augmentation (mpc_explicit.py:383-466): the reference's
+    CtrlPassthroughDynamics (dynamics.py:133-156) on device, state
+    [u_{t-1}; x_t] of n = mlp.n + mlp.m entries, m = mlp.m; .mlp is the network.
+    Its rollout, linearisation and line search are the dilqr_mlp_slew_* /
+    dilqr_mlp2_slew_* entry points (csrc/dilqr_ctrl_through.h); it stands
+    wherever a handle does (lqr_forward, mpc_solve_unfused: the four launches
+    per iteration).  None when the augmented (n, m) is not a shape the kernels
+    are compiled for."""
+    if not isinstance(mlp, MLP_MODELS):
+        raise TypeError("dilqr: slew_dynamics takes an MlpModel or an Mlp2Model (NNDynamics.device_model)")
+    if (mlp.n + mlp.m, mlp.m) not in N.LANE_SHAPES:
+        return None
+    return Dynamics(mlp, mlp.n + mlp.m, mlp.m, slew=True)
+
+
+def slew_cost_block(T, B, n, m, slew_rate_penalty, device, dtype):
+    """The slew-rate penalty's own cost matrix [T,B,n+2m,n+2m] on
+    [u_{t-1}; x_t; u_t] (mpc_explicit.py:383-466): gamma [[I, -I], [-I, I]] on
+    the two controls, zero elsewhere."""
+    d = n + 2 * m
+    sC = torch.zeros(T, B, d, d, device=device, dtype=dtype)
+    half_gamI = slew_rate_penalty * torch.eye(m, device=device, dtype=dtype).expand(T, B, m, m)
+    sC[:, :, :m, :m] = half_gamI
+    sC[:, :, -m:, :m] = -half_gamI
+    sC[:, :, :m, -m:] = -half_gamI
+    sC[:, :, -m:, -m:] = half_gamI
+    return sC
+
+
+def slew_prev_ctrl(prev_ctrl, B, m, device, dtype):
+    """MPC's prev_ctrl (None = zeros, [m], [B,m] or [1,B,m]) as [1,B,m] or a
+    view that expands to it (mpc_explicit.py:383-466)."""
+    if prev_ctrl is None:
+        return torch.zeros(1, B, m, device=device, dtype=dtype)
+    prev_u = prev_ctrl.detach()
+    if prev_u.ndimension() == 1:
+        prev_u = prev_u.unsqueeze(0)
+    if prev_u.ndimension() == 2:
+        prev_u = prev_u.unsqueeze(0)
+    return prev_u
+
+
+def slew_problem(x_init, C, c, slew_rate_penalty, prev_ctrl, m):
+    """The plain MPC problem the slew-rate augmentation solves
+    (mpc_explicit.py:383-466): (x~_init [B,n+m] = [prev_ctrl; x_init],
+    C~ [T,B,n+2m,n+2m] = C padded on the left and top + slew_cost_block,
+    c~ [T,B,n+2m] = [0; c]) for x_init [B,n], C [T,B,n+m,n+m], c [T,B,n+m].
+    Plain torch ops (they carry C's, c's and x_init's gradient);
+    generic.slew_augment builds its own from these."""
+    T, B = C.shape[:2]
+    n = x_init.shape[1]
+    dev, dt = C.device, C.dtype
+    _C = slew_cost_block(T, B, n, m, slew_rate_penalty, dev, dt) + torch.nn.functional.pad(C, (m, 0, m, 0))
+    _c = torch.cat((torch.zeros(T, B, m, device=dev, dtype=dt), c), 2)
+    prev_u = slew_prev_ctrl(prev_ctrl, B, m, dev, dt)
+    _x_init = torch.cat((prev_u[0].expand(B, m), x_init), 1)
+    return _x_init, _C, _c
 
 
 def generic_model_id(dx):
@@ -616,7 +695,7 @@ def lqr_forward(model_id, theta, x_init, C, c, x, u, K, k, F=None, f=None, u_low
     du_sq = torch.empty(T, m, B, device=dev)
     dyn = Dynamics.of(model_id, theta, n, m, F, f)
     if dyn.mlp is not None:
-        dyn.mlp.check(x, u)
+        dyn.check(x, u)
         d = n + m
         if (tuple(x_init.shape), tuple(C.shape), tuple(c.shape), tuple(K.shape), tuple(k.shape)) != (
                 (B, n), (T, B, d, d), (T, B, d), (T, B, m, n), (T, B, m)):
@@ -917,8 +996,12 @@ def mlp_solve_route(dyn, B, lqr_iter, u_zero_I, verbose):
     min(SMALL_BATCH_MAX, MLP_SMALL_MAX_BATCH), a shape in N.MLP_SMALL_SHAPES); "fused", the fused iteration +
     dilqr_mpc_update_best_f32 per iteration; "unfused", the four launches per
     iteration: everything but a one-hidden-layer MlpModel, a control mask,
-    verbose, MLP_FUSED off, a batch above MLP_FUSED_MAX_BATCH."""
+    verbose, MLP_FUSED off, a batch above MLP_FUSED_MAX_BATCH; and a handle
+    under the slew-rate augmentation (slew_dynamics), whose fused iteration is
+    not built."""
     mlp = dyn.mlp if isinstance(dyn, Dynamics) else dyn
+    if getattr(dyn, "slew", False):
+        return "unfused"
     if not MLP_FUSED or not isinstance(mlp, MlpModel) or u_zero_I is not None or verbose > 0:
         return "unfused"
     if B < 1 or lqr_iter < 1:
@@ -1069,7 +1152,8 @@ def lqr_adjoint(C, c, F, x, u, dl_dx, dl_du, u_lower=None, u_upper=None, m_solve
 
 def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=None, u_lower=None,
                       u_upper=None, lqr_iter=10, eps=1e-7, linesearch_decay=0.2, max_linesearch_iter=10,
-                      not_improved_lim=5, best_cost_eps=1e-4, check_every=8, u_zero_I=None, verbose=0):
+                      not_improved_lim=5, best_cost_eps=1e-4, check_every=8, u_zero_I=None, verbose=0,
+                      delta_u=None):
     """The same outer loop with the unfused kernels (linearise -> F in HBM ->
     Riccati -> rollout/line search).  Used for LinDx dynamics (classic mpc.MPC,
     the adjoint engines), MPC(u_zero_I=...) and to cross-check the fused
@@ -1084,6 +1168,17 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
     iteration (Dynamics.fused_iterate) + the best/stop rule per iteration, or
     the whole solve in one launch; both fill the same MPCWorkspace fields with
     the four launches' bits (best_x, best_u, best_cost, best_du, fdn, ctrl).
+    A handle of slew_dynamics (with slew_problem's x_init, C, c) solves
+    MPC(slew_rate_penalty=...) on a network: the four launches, the rollout,
+    linearisation and line search being the dilqr_mlp*_slew_* entry points.
+
+    delta_u: the trust region of MPC(delta_u=...) (bounds required, as in the
+    reference, lqr_step_explicit.py:197), for any dynamics, always the four
+    launches: every iteration's sweep takes the box relative to the current u
+    clipped to +-delta_u (132-135; delta_sweep) and its line search clamps to
+    u_t +- delta_u cut to the bounds (205-213), both formed from the current
+    controls by torch ops on the stream and passed as tensor bounds; no host
+    synchronisation besides the stop poll.
 
     The host polls the stop flag every `check_every` iterations: up to
     check_every - 1 iterations after the stop rule fired still run their
@@ -1103,7 +1198,10 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
                              f"C {tuple(C.shape)}, c {tuple(c.shape)} at T = {T}")
         if x_init.device != dyn.mlp.device:
             raise RuntimeError("dilqr: MLP weights and inputs are on different devices")
-    route = mlp_solve_route(dyn, B, lqr_iter, u_zero_I, verbose)
+    if delta_u is not None and u_lower is None:
+        raise NotImplementedError("dilqr: delta_u without u_lower is unimplemented in the reference too "
+                                  "(lqr_step_explicit.py:197)")
+    route = mlp_solve_route(dyn, B, lqr_iter, u_zero_I, verbose) if delta_u is None else "unfused"
     ws = MPCWorkspace(T, B, n, m, dev, fused=route != "unfused")
     s = N.stream(dev)
     bounds, keep = N.make_bounds(u_lower, u_upper)          # (keep: alive until every launch is queued)
@@ -1143,8 +1241,13 @@ def mpc_solve_unfused(model_id, theta, x_init, C, c, T, F=None, f=None, u_init=N
     ran = 0
     for i in range(lqr_iter):
         Fi, _ = dyn.linearize(ws.xa, ws.ua)
-        K, k, _ = lqr_backward(C, c, Fi, n, m, x=ws.xa, u=ws.ua, u_lower=u_lower, u_upper=u_upper,
-                               u_zero_I=zI if u_lower is None else None)
+        if delta_u is None:
+            K, k, _ = lqr_backward(C, c, Fi, n, m, x=ws.xa, u=ws.ua, u_lower=u_lower, u_upper=u_upper,
+                                   u_zero_I=zI if u_lower is None else None)
+        else:
+            # the trust region around this iteration's controls, for the sweep and for the rollout
+            K, k, _ = delta_sweep(C, c, Fi, n, m, ws.xa, ws.ua, u_lower, u_upper, delta_u=delta_u)
+            bounds, keep = N.make_bounds(*delta_u_rollout_bounds(u_lower, u_upper, ws.ua, delta_u))
         # from iteration 1 the old cost is the previous line search's value for
         # the accepted candidate (ws.cost), as the fused MPC kernel takes it
         dyn.line_search(x_init, C, c, ws.xa, ws.ua, K, k, bounds, zI, linesearch_decay, max_linesearch_iter,

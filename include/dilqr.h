@@ -695,6 +695,54 @@ int dilqr_mlp2_implicit_backward_f32(int n, int m, int T, int B, dilqr_mlp2 mlp,
                                      dilqr_bounds bounds, float* ws, float* dx_init, float* dC,
                                      float* dc, float* dF, float* df, void* stream);
 
+/* ---- learned dynamics under the slew-rate augmentation ----------------------- */
+/* MPC(slew_rate_penalty=...) on a network is a plain solve of the augmented
+   system of solve_lqr_subproblem's slew-rate branch, mpc_explicit.py:383-466,
+   with the reference's CtrlPassthroughDynamics, dynamics.py:133-156, as its
+   dynamics: the state is x~_t = [u_{t-1}; x_t] (n + m wide),
+     x~_{t+1} = [u_t; mlp(x_t, u_t)],
+   and the Jacobian with respect to [u_{t-1}; x_t; u_t] is the reference's _F,
+     [ 0 0 I ]   (m rows)
+     [ 0 R S ]   (n rows, [R S] the network's, dilqr_mlp_linear_dyn_f32).
+   These entry points evaluate that model.  (n, m) are the NETWORK's; every
+   state buffer (x_init, x, x_out, K's columns, the rows of F and f) is n + m
+   wide and C, c are those of the augmented system ([T,B,n+2m,n+2m],
+   [T,B,n+2m]); the argument lists are otherwise those of dilqr_mlp_rollout_f32,
+   dilqr_mlp_linearize_f32 and dilqr_mlp_lqr_forward_f32, and their outputs feed
+   dilqr_lqr_backward_f32 and dilqr_mpc_update_best_f32 at (n + m, m).  The
+   lower n entries of a rolled-out state and the lower n rows of F, f carry the
+   bits of the plain entry points at the same (x_t, u_t); the upper m entries
+   are the previous control, copied, the upper rows of F are exactly [0 0 I]
+   and those of f exactly 0.
+   Errors as their counterparts, all before any launch; DILQR_E_SHAPE also when
+   (n + m, m) is not a shape the one-lane kernels are compiled for — of the
+   networks' shapes (4,3), (6,1) and (6,2).  B = 0 launches nothing. */
+int dilqr_mlp_slew_rollout_f32(int n, int m, int T, int B, dilqr_mlp mlp, const float* x_init,
+                               const float* u, float* x_out, void* stream);
+int dilqr_mlp_slew_linearize_f32(int n, int m, int T, int B, dilqr_mlp mlp, const float* x,
+                                 const float* u, float* F, float* f, void* stream);
+int dilqr_mlp_slew_lqr_forward_f32(int n, int m, int T, int B, dilqr_mlp mlp, const float* x_init,
+                                   const float* C, const float* c, const float* x,
+                                   const float* u, const float* K, const float* k,
+                                   dilqr_bounds bounds, const unsigned char* u_zero_I,
+                                   float linesearch_decay, int max_linesearch_iter,
+                                   float* x_out, float* u_out, float* cost, float* du_sq,
+                                   float* alpha, const float* old_cost, void* stream);
+/* The same for the two-hidden-layer network (dynamics.py:133-156 over
+   dilqr_mlp2, mpc_explicit.py:383-466); each launch keeps the first layer's
+   activations in LDS as the dilqr_mlp2_* entry points do. */
+int dilqr_mlp2_slew_rollout_f32(int n, int m, int T, int B, dilqr_mlp2 mlp, const float* x_init,
+                                const float* u, float* x_out, void* stream);
+int dilqr_mlp2_slew_linearize_f32(int n, int m, int T, int B, dilqr_mlp2 mlp, const float* x,
+                                  const float* u, float* F, float* f, void* stream);
+int dilqr_mlp2_slew_lqr_forward_f32(int n, int m, int T, int B, dilqr_mlp2 mlp, const float* x_init,
+                                    const float* C, const float* c, const float* x,
+                                    const float* u, const float* K, const float* k,
+                                    dilqr_bounds bounds, const unsigned char* u_zero_I,
+                                    float linesearch_decay, int max_linesearch_iter,
+                                    float* x_out, float* u_out, float* cost, float* du_sq,
+                                    float* alpha, const float* old_cost, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

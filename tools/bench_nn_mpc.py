@@ -18,7 +18,17 @@ at the largest batch, with its bytes and FLOPs per row.  --hidden 64,64 takes a
 network with two hidden layers instead: the device arm then also turns
 generic.DEVICE_MLP_DEEP on (csrc/tu_mlp2.hip), the torch arm is the same loop.
 
+--slew-rate-penalty G or --delta-u D (one of them) times the same solve with that
+MPC option.  Two arms then: "torch", the path such a solve takes as shipped
+(generic.DEVICE_MLP_SLEW / DEVICE_MLP_DELTA_U off: the torch loop, its rollouts
+and linearisation on the device model for one hidden layer, every line search
+T sequential evaluations of the Module), and "device", the option's switch on
+(and DEVICE_MLP_DEEP for two hidden layers): ops.mpc_solve_unfused on
+ops.slew_dynamics, or with delta_u, four launches per iteration.  The fused arms
+do not apply, and the linearisation kernel is not timed again.
+
     python tools/bench_nn_mpc.py [--batches 32,4096,65536] [--arms device,fused] [--hidden 64,64] [--out FILE]
+                                 [--slew-rate-penalty G | --delta-u D]
 """
 import argparse
 import os
@@ -60,11 +70,12 @@ def problem(B, dev):
     return x0.to(dev), C.to(dev), c.to(dev)
 
 
-def solver(B):
+def solver(B, slew_rate_penalty=None, delta_u=None):
     import dilqr.mpc as cmpc
     return cmpc.MPC(N_STATE, N_CTRL, T, lqr_iter=LQR_ITER, grad_method=cmpc.GradMethods.ANALYTIC, u_lower=-1.0,
                     u_upper=1.0, n_batch=B, eps=0.0, not_improved_lim=10 ** 9, exit_unconverged=False,
-                    detach_unconverged=False, linesearch_decay=0.2, max_linesearch_iter=10, verbose=-1)
+                    detach_unconverged=False, linesearch_decay=0.2, max_linesearch_iter=10, verbose=-1,
+                    slew_rate_penalty=slew_rate_penalty, delta_u=delta_u)
 
 
 def timed_solve(mpc, x0, cost, dx):
@@ -85,9 +96,17 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--budget", type=float, default=60.0, help="seconds of timed solves per batch and arm")
     ap.add_argument("--hidden", default=str(HIDDEN), help="hidden widths: one (default) or two, as 64,64")
-    ap.add_argument("--arms", default="torch,device,fused", help="arms to time, the first one the baseline")
+    ap.add_argument("--arms", default=None, help="arms to time, the first one the baseline (default torch,device,"
+                    "fused; torch,device with an MPC option)")
+    ap.add_argument("--slew-rate-penalty", type=float, default=None, help="MPC(slew_rate_penalty=G)")
+    ap.add_argument("--delta-u", type=float, default=None, help="MPC(delta_u=D)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    option = args.slew_rate_penalty is not None or args.delta_u is not None
+    if args.slew_rate_penalty is not None and args.delta_u is not None:
+        sys.exit("bench_nn_mpc: --slew-rate-penalty and --delta-u do not go together (no device route for both)")
+    if args.arms is None:
+        args.arms = "torch,device" if option else "torch,device,fused"
     hidden = [int(h) for h in args.hidden.split(",")]
     if len(hidden) not in (1, 2):
         sys.exit("bench_nn_mpc: --hidden takes one or two widths")
@@ -102,6 +121,8 @@ def main():
     lines = [f"# bench_nn_mpc  commit {commit()}  lib {os.environ.get('DILQR_LIB', 'dilqr/libdilqr.so')}",
              f"# NNDynamics({N_STATE},{N_CTRL},{hidden},sigmoid) T={T} lqr_iter={LQR_ITER} fixed-count, u in [-1,1], "
              f"dense SPD cost; one mpc.MPC.forward under no_grad; device events; ms",
+             *([f"# MPC option: slew_rate_penalty={args.slew_rate_penalty} delta_u={args.delta_u}; arm torch = the "
+                f"option's switch off (as shipped), arm device = on"] if option else []),
              f"# {torch.cuda.get_device_name(0)}  torch {torch.__version__}",
              "B        arm     n   median_ms      min_ms      max_ms   speedup   max_rel_cost_diff"]
 
@@ -123,9 +144,17 @@ def main():
     arms = [a for a in args.arms.split(",") if a]
     if not arms or any(a not in ARMS for a in arms):
         sys.exit("bench_nn_mpc: --arms takes a list of " + ",".join(ARMS))
+    if option and any(a not in ("torch", "device") for a in arms):
+        sys.exit("bench_nn_mpc: with an MPC option the arms are torch and device")
 
     def arm(name):
         flag, fused = ARMS[name]
+        if option:
+            # the shipped route against the option's switch (DEVICE_MLP stays on in both)
+            generic.DEVICE_MLP_SLEW = flag and args.slew_rate_penalty is not None
+            generic.DEVICE_MLP_DELTA_U = flag and args.delta_u is not None
+            generic.DEVICE_MLP_DEEP = flag and deep
+            return
         generic.DEVICE_MLP = flag
         generic.DEVICE_MLP_DEEP = flag and deep
         ops.MLP_FUSED = fused
@@ -133,7 +162,7 @@ def main():
 
     for B in [int(b) for b in args.batches.split(",")]:
         x0, C, c = problem(B, dev)
-        cost, mpc = QuadCost(C, c), solver(B)
+        cost, mpc = QuadCost(C, c), solver(B, args.slew_rate_penalty, args.delta_u)
         times, costs = {a: [] for a in arms}, {}
         for a in arms:
             arm(a)
@@ -151,6 +180,7 @@ def main():
                 times[a].append(ms)
                 costs[a] = cs
         generic.DEVICE_MLP, generic.DEVICE_MLP_DEEP, ops.MLP_FUSED = True, False, True
+        generic.DEVICE_MLP_SLEW = generic.DEVICE_MLP_DELTA_U = False
         ops.MLP_SMALL_MAX_BATCH = small_max
         base = arms[0]                                     # speed-up and cost difference against the first arm
         med = {a: statistics.median(times[a]) for a in arms}
@@ -174,6 +204,12 @@ def main():
                  f"costs {'equal bits' if same else 'DIFFER'}")
         del x0, C, c, cost
         torch.cuda.empty_cache()
+    if option:
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
     # the linearisation kernel alone at the largest batch
     B = max(int(b) for b in args.batches.split(","))
     md = dx.device_model(torch.zeros(1, device=dev), deep=deep)
