@@ -905,13 +905,169 @@ def case_complex():
             save(f"complex_{tname(dt)}", **out)
 
 
+# --------------------------------------------------------------------------
+# N. dense, time-varying and asymmetric costs (tests/cost_cases.py): sweeps
+#    through LQRStepFn.forward and mpc_explicit.MPC solves.  Writes only
+#    costs_{f64,f32}.npz; the costs themselves are not stored (seeds + checksums)
+# --------------------------------------------------------------------------
+def _cost_cases():
+    for p_ in (os.path.dirname(OUT), os.path.dirname(os.path.dirname(OUT))):
+        if p_ not in sys.path:
+            sys.path.append(p_)
+    import cost_cases
+    from oracle import models as omodels
+
+    def true_obj(mname):
+        q, p = omodels.MODELS[mname].true_obj()
+        rq, rp = model(mname).get_true_obj()          # the oracle's restatement is the reference's
+        assert np.allclose(q, np_(rq), rtol=1e-6, atol=0) and np.allclose(p, np_(rp), rtol=1e-6, atol=0)
+        return q, p
+    return cost_cases, true_obj
+
+
+def replay_spread32(CC, name, x0, C, c):
+    """Each problem's fp32 conditioning under decision replay, measured with no
+    kernel in the loop: the numpy oracle run in float32 (one problem at a time,
+    as the device solves), its line-search and best-iterate decisions forced on
+    the fp64 oracle, and the relative cost difference per problem: what the
+    GPU tests' check_against_forced_oracle measures of the device."""
+    from oracle import models as omodels
+    from oracle import mpc as ompc
+    mname, T, _B, it, bounds, decay, mls, _mixed = CC.MPC_CASES[name]
+    lo, hi = bounds if bounds else (None, None)
+    kw = dict(u_lower=lo, u_upper=hi, lqr_iter=it, eps=0.0, not_improved_lim=10 ** 9, linesearch_decay=decay,
+              max_linesearch_iter=mls, per_problem=True)
+    f = np.float32
+    tr = []
+    _, _, c32, _ = ompc.mpc_forward(omodels.MODELS[mname], x0.astype(f), C.astype(f), c.astype(f), T, trace=tr, **kw)
+    force = lambda i: (tr[i]["alpha_free"].astype(np.float64), tr[i]["take_free"])  # noqa: E731
+    _, _, c64, _ = ompc.mpc_forward(omodels.MODELS[mname], x0, C, c, T, force=force, **kw)
+    return np.abs(c32 - c64) / np.maximum(1.0, np.abs(c64))
+
+
+def sweep_via_forward(step_mod, n, m, T, C, c, F, x, u, **kw):
+    """K, k (natural time order) of the sweep as LQRStepFn.forward runs it from
+    current_x, current_u: c_back is formed inside forward
+    (lqr_step_explicit.py:630-636, lqr_step_backup.py:388-394).  The closure's
+    lqr_backward is wrapped to keep its result and lqr_forward (which needs
+    true dynamics) is replaced by a stand-in."""
+    fn = step_mod.LQRStep(n, m, T, current_x=x, current_u=u, **kw).__self__.forward
+    cells = dict(zip(fn.__code__.co_freevars, fn.__closure__))
+    inner = cells["lqr_backward"].cell_contents
+    got = {}
+
+    def keep(ctx, *a):
+        got["Ks"], got["ks"], nqp = inner(ctx, *a)
+        return got["Ks"], got["ks"], nqp
+    none = types.SimpleNamespace(costs=None, full_du_norm=None, mean_alphas=None)
+    cells["lqr_backward"].cell_contents = keep
+    cells["lqr_forward"].cell_contents = lambda *a: (None, None, none)
+    fn(types.SimpleNamespace(save_for_backward=lambda *a: None), x[0], C, c, F)
+    return np_(got["Ks"][::-1]), np_(got["ks"][::-1])
+
+
+COST_SWEEP_SEEDS = {"s31": 31, "s51": 51, "s42": 42, "s43": 43, "s133": 133}
+# first seed tried per MPC case; the generator walks up from it until the
+# conditioning condition below holds, and stores the seed it used
+COST_MPC_SEED0 = {"cart_mixed_unc": 0, "cart_mixed_box10": 0, "pend_mixed_box": 0, "rocket_dense_unc": 0,
+                  "rocket_dense_box20": 0, "rocket_diag_it10": 0}
+COST_SPREAD_WIDE, COST_SPREAD_CAP = 1e-5, 1e-3     # at most 1 problem in 16 above WIDE, none above CAP
+# A second, stricter condition on the same inputs.  The GPU tests hold a
+# problem's cost to max(1e-5, 3 x the reference's fp32-vs-fp64 spread), which
+# takes one fp32 run's error to bound another's within 3x.  The reference's
+# free-running fp32 solve is a single sample and can understate a problem's
+# sensitivity (seed 0, cart_mixed_box10 problem 0: reference spread 2.4e-6,
+# the float32 numpy oracle under decision replay 4.4e-5; the swing-up error
+# grows ~10x per iteration over the last iterations there).  So a fixture is
+# used only if a second fp32 implementation that is not under test, the numpy
+# oracle in float32 (replay_spread32), meets that bar with the same factor 3
+# to spare on every problem.
+COST_REPLAY_MARGIN = 3.0
+
+
+def run_mpc_cost(CC, name, dt, x0, C, c):
+    mname, T, _B, it, bounds, decay, mls, _mixed = CC.MPC_CASES[name]
+    dx = model(mname)
+    kw = {} if bounds is None else dict(u_lower=bounds[0], u_upper=bounds[1])
+    m = R.mpc_explicit.MPC(dx.n_state, dx.n_ctrl, T, lqr_iter=it, eps=0.0, not_improved_lim=10 ** 9,
+                           linesearch_decay=decay, max_linesearch_iter=mls, exit_unconverged=False,
+                           detach_unconverged=False, verbose=-1, u_init=None,
+                           grad_method=R.mpc_explicit.GradMethods.ANALYTIC, **kw)
+    with torch.no_grad(), contextlib.redirect_stdout(io.StringIO()):
+        x, u, costs = m(torch.tensor(x0, dtype=dt), R.mpc_explicit.QuadCost(
+            torch.tensor(C, dtype=dt), torch.tensor(c, dtype=dt)), dx)
+    return np_(x).astype(np.float64), np_(u).astype(np.float64), np_(costs).astype(np.float64)
+
+
+def case_costs():
+    print("N. dense / time-varying / asymmetric costs")
+    CC, true_obj = _cost_cases()
+    out = {torch.float64: {}, torch.float32: {}}
+    rel = lambda a, b: np.max(np.abs(a - b)) / max(1.0, np.max(np.abs(b)))  # noqa: E731
+    # ---- sweeps
+    for name, seed in COST_SWEEP_SEEDS.items():
+        pr = CC.sweep_problem(name, true_obj, seed)
+        n, m, T = pr["n"], pr["m"], CC.SWEEP_T
+        for dt in out:
+            o = out[dt]
+            o[f"{name}_seed"] = np.array(seed)
+            o[f"{name}_sum"] = CC.checksum(pr["C"], pr["c"], pr["C_box"], pr["c_box"], pr["F"], pr["x"], pr["u"])
+            with default_dtype(dt), torch.no_grad():
+                t_ = lambda a: torch.tensor(a, dtype=dt)  # noqa: E731
+                F, x, u = t_(pr["F"]), t_(pr["x"]), t_(pr["u"])
+                for mode in CC.SWEEP_MODES[name]:
+                    C, c = (pr["C_box"], pr["c_box"]) if mode == "box" else (pr["C"], pr["c"])
+                    mod = R.lqr_step_backup if mode == "chol" else R.lqr_step_explicit
+                    kw = dict(u_lower=-CC.SWEEP_BOX, u_upper=CC.SWEEP_BOX) if mode == "box" else {}
+                    K, k = sweep_via_forward(mod, n, m, T, t_(C), t_(c), F, x, u, **kw)
+                    assert np.isfinite(K).all() and np.isfinite(k).all(), (name, mode)
+                    o[f"{name}_{mode}_K"], o[f"{name}_{mode}_k"] = K, k
+        print(f"  sweep {name}: modes {CC.SWEEP_MODES[name]}, fp32-vs-fp64 K " +
+              ", ".join(f"{mo} {rel(out[torch.float32][f'{name}_{mo}_K'], out[torch.float64][f'{name}_{mo}_K']):.1e}"
+                        for mo in CC.SWEEP_MODES[name]))
+    # ---- MPC solves
+    for name, (mname, T, Bf, it, bounds, decay, mls, mixed) in CC.MPC_CASES.items():
+        for seed in range(COST_MPC_SEED0[name], COST_MPC_SEED0[name] + 40):
+            x0 = CC.f32(xinit_for(mname, Bf, np.random.RandomState(seed)))
+            C, c = CC.mpc_costs(name, true_obj, seed)
+            res = {}
+            for dt in out:
+                with default_dtype(dt):
+                    res[dt] = run_mpc_cost(CC, name, dt, x0, C, c)
+            (x64, u64, c64), (x32, u32, c32) = res[torch.float64], res[torch.float32]
+            spread = np.abs(c32 - c64) / np.maximum(1.0, np.abs(c64))
+            ok = np.isfinite(c64).all() and np.isfinite(c32).all() and \
+                int((spread > COST_SPREAD_WIDE).sum()) <= Bf // 16 and not (spread > COST_SPREAD_CAP).any()
+            replay = replay_spread32(CC, name, x0, C, c)
+            bar = np.maximum(COST_SPREAD_WIDE, 3 * spread) / COST_REPLAY_MARGIN
+            ok = ok and bool(np.all(replay < bar))
+            print(f"  mpc {name} seed {seed}: spread max {spread.max():.2e}, above {COST_SPREAD_WIDE:g}: "
+                  f"{int((spread > COST_SPREAD_WIDE).sum())}/{Bf}, x {rel(x32, x64):.1e}, u {rel(u32, u64):.1e}; "
+                  f"float32 oracle replay max {replay.max():.2e}, over its bar: {np.flatnonzero(replay >= bar)}"
+                  f"{'' if ok else '  -> next seed'}")
+            if ok:
+                break
+        # the condition on the inputs (the cap is fixed; a seed that misses it is not used)
+        assert ok, name
+        assert int((spread > COST_SPREAD_WIDE).sum()) <= Bf // 16 and spread.max() <= COST_SPREAD_CAP
+        assert np.all(replay < np.maximum(COST_SPREAD_WIDE, 3 * spread) / COST_REPLAY_MARGIN)
+        for dt, (x, u, costs) in res.items():
+            out[dt].update({f"{name}_seed": np.array(seed), f"{name}_sum": CC.checksum(C, c), f"{name}_x0": x0,
+                            f"{name}_x": x, f"{name}_u": u, f"{name}_costs": costs,
+                            f"{name}_spread": spread, f"{name}_replay32": replay, f"{name}_spread_x": np.array(rel(x32, x64)),
+                            f"{name}_spread_u": np.array(rel(u32, u64))})
+    for dt in out:
+        save(f"costs_{tname(dt)}", **out[dt])
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["models", "riccati", "pnqp", "lqrstep", "mpc", "adjoint", "implicit",
-                             "implicit25", "datasets", "il", "generic", "api", "complex", "stepgen"]
+                             "implicit25", "datasets", "il", "generic", "api", "complex", "stepgen", "costs"]
     table = {"models": case_models, "riccati": case_riccati, "pnqp": case_pnqp,
              "lqrstep": case_lqrstep, "mpc": case_mpc, "mpc_iterates": case_mpc_iterates,
              "adjoint": case_classic_adjoint,
              "implicit": case_implicit, "implicit25": case_implicit25, "datasets": case_datasets, "il": case_il,
-             "generic": case_generic, "api": case_api, "complex": case_complex, "stepgen": case_stepgen}
+             "generic": case_generic, "api": case_api, "complex": case_complex, "stepgen": case_stepgen,
+             "costs": case_costs}
     for w in which:
         table[w]()

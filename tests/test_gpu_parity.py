@@ -210,14 +210,21 @@ MPC_CASES = {
 }
 
 
-def run_gpu_mpc(x0, mname, T, it, bounds, eps, nil, decay, mls, fused=True):
+def device_cost(dx, T, B, cost):
+    """The model's true diagonal objective repeated over (t, b), or cost = (C, c)
+    ([T,B,d,d], [T,B,d] arrays) as contiguous fp32 device tensors."""
+    if cost is None:
+        q, p = dx.get_true_obj()
+        return torch.diag(q).repeat(T, B, 1, 1).to(DEV).contiguous(), p.repeat(T, B, 1).to(DEV).contiguous()
+    return gpu(cost[0]).contiguous(), gpu(cost[1]).contiguous()
+
+
+def run_gpu_mpc(x0, mname, T, it, bounds, eps, nil, decay, mls, fused=True, cost=None):
     import dilqr
     from dilqr import ops
     dx = dilqr_models()[mname]()
     B = x0.shape[0]
-    q, p = dx.get_true_obj()
-    C = torch.diag(q).repeat(T, B, 1, 1).to(DEV)
-    c = p.repeat(T, B, 1).to(DEV)
+    C, c = device_cost(dx, T, B, cost)
     lo, hi = bounds if bounds else (None, None)
     if fused:
         m = dilqr.MPC(dx.n_state, dx.n_ctrl, T, u_lower=lo, u_upper=hi, lqr_iter=it, eps=eps,
@@ -232,19 +239,18 @@ def run_gpu_mpc(x0, mname, T, it, bounds, eps, nil, decay, mls, fused=True):
     return ws.best_x, ws.best_u, ws.best_cost
 
 
-def gpu_solve_with_decisions(x0, mname, T, it, bounds, eps, nil, decay, mls):
+def gpu_solve_with_decisions(x0, mname, T, it, bounds, eps, nil, decay, mls, cost=None, flags_out=None):
     """The device-resident solve run one iteration at a time (the stop-rule
     path), recording each iteration's per-problem decisions as the kernels
     took them: the accepted step size (S.alpha) and whether the iterate became
     the best one (S.improved != 0).  Returns best x, u, cost and the decisions
-    of the iterations that ran."""
+    of the iterations that ran.  cost = (C, c): that cost in place of the
+    model's true objective; flags_out (a list): gets the solve's cost_sym [B]."""
     from dilqr import _native as N
     from dilqr import ops
     dx = dilqr_models()[mname]()
     B, n, m = x0.shape[0], dx.n_state, dx.n_ctrl
-    q, p = dx.get_true_obj()
-    C = torch.diag(q).repeat(T, B, 1, 1).to(DEV).contiguous()
-    c = p.repeat(T, B, 1).to(DEV).contiguous()
+    C, c = device_cost(dx, T, B, cost)
     x0g = gpu(x0)
     theta = ops.theta_of(dx, x0g)
     lo, hi = bounds if bounds else (None, None)
@@ -258,11 +264,13 @@ def gpu_solve_with_decisions(x0, mname, T, it, bounds, eps, nil, decay, mls):
         takes.append(cpu(sv.improved) != 0)
     ran = sv.iterations if sv.stopped else it
     x, u = sv.gather_best()
+    if flags_out is not None:
+        flags_out.append(cpu(sv.cost_sym).astype(int))
     return x, u, sv.best_cost.clone(), alphas[:ran], takes[:ran]
 
 
 def check_against_forced_oracle(M, x0, T, bounds, decay, mls, x, u, costs, alphas, takes, label,
-                                cost_tol=1e-5, traj_tol=1e-4, tie=1e-5, ref_spread=None):
+                                cost_tol=1e-5, traj_tol=1e-4, tie=1e-5, ref_spread=None, cost=None, detail=None):
     """Parity by decision replay.  (1) The fp64 oracle, made to take the GPU's
     decisions (its step sizes and best-iterate updates, oracle/mpc.py `force`),
     must reproduce the GPU's best trajectories and costs: what remains is fp32
@@ -274,10 +282,16 @@ def check_against_forced_oracle(M, x0, T, bounds, decay, mls, x, u, costs, alpha
     Prints the measured errors and the count of near-tie flips.
     ref_spread (per problem, optional): the reference's own fp32-vs-fp64 cost
     difference on the same problem; a problem whose cost the reference itself
-    cannot hold to cost_tol in fp32 is held to 3x that spread instead."""
+    cannot hold to cost_tol in fp32 is held to 3x that spread instead.
+    cost = (C, c): that cost in place of the model's true objective.
+    detail (a dict): gets the per-problem errors (cost [B]; u, x [B], each
+    relative to the batch's max magnitude, as the assertions) and flip counts."""
     B = x0.shape[0]
-    q, p = M.true_obj()
-    Co, co = ompc.expand_cost(np.diag(q), p, T, B)
+    if cost is None:
+        q, p = M.true_obj()
+        Co, co = ompc.expand_cost(np.diag(q), p, T, B)
+    else:
+        Co, co = (np.asarray(a, np.float64) for a in cost)
     lo, hi = bounds if bounds else (None, None)
     trace = []
     xo, uo, cso, _ = ompc.mpc_forward(M, x0, Co, co, T, u_lower=lo, u_upper=hi, lqr_iter=len(alphas), eps=0.0,
@@ -297,6 +311,9 @@ def check_against_forced_oracle(M, x0, T, bounds, decay, mls, x, u, costs, alpha
         assert np.all(tr["best_margin"][dif_t] < tie), (label, i, np.flatnonzero(dif_t), tr["best_margin"][dif_t])
     print(f"\n[{label}] forced-decision oracle: max rel cost err {cerr.max():.2e}, u {uerr:.2e}, x {xerr:.2e}; "
           f"near-tie decision flips {flips}/{total}")
+    if detail is not None:
+        detail.update(cost=cerr, u=np.abs(cpu(u) - uo).max(axis=(0, 2)) / max(1.0, np.abs(uo).max()),
+                      x=np.abs(cpu(x) - xo).max(axis=(0, 2)) / max(1.0, np.abs(xo).max()), flips=flips, total=total)
     tol = np.full(B, cost_tol) if ref_spread is None else np.maximum(cost_tol, 3 * ref_spread)
     wide = np.flatnonzero(tol > cost_tol)
     if wide.size:
@@ -1184,7 +1201,8 @@ def test_rocket_fused_iteration_equals_unfused_tensor_bounds(golden):
 def test_rocket_mpc_full_size_batch_independence(B):
     """Config 3 shape (B=32768, T=30) and 4x that batch on one GPU: a solve
     over the whole batch returns, for a sample of problems (the last one
-    included), what solving those problems alone returns."""
+    included), what solving those problems alone returns.  At B = 32768 the
+    sample is also held to the fp64 oracle by decision replay."""
     import dilqr
     from dilqr.env_dx.rocket import RocketDx
     T = 30
@@ -1215,6 +1233,14 @@ def test_rocket_mpc_full_size_batch_independence(B):
     # the gain-record layout may depend on B
     idx_t = torch.tensor(idx, device=DEV)
     assert torch.equal(cost[idx_t], cs) and torch.equal(u[:, idx_t], us) and torch.equal(x[:, idx_t], xs)
+    if B == 32768:
+        # the sampled problems against the fp64 oracle by decision replay: the
+        # per-iteration path on them alone records the decisions and gives the
+        # bits of the whole-batch solve
+        xd, ud, cd, alphas, takes = gpu_solve_with_decisions(x0[idx], "rocket", T, 5, None, 0.0, 10 ** 9, 0.2, 5)
+        assert same_bits(xd, xs) and same_bits(ud, us) and same_bits(cd, cs)
+        check_against_forced_oracle(omodels.Rocket, cpu(gpu(x0[idx])), T, None, 0.2, 5, xd, ud, cd, alphas, takes,
+                                    "rocket full size slice")
 
 
 # ------------------------------------------------------------------ standalone fused iteration

@@ -293,3 +293,54 @@ def test_implicit_backward_fast_f64(golden, tag):
     assert rel(dth, g[f"{tag}_dtheta_b"]) < tol
     assert rel(dC, g[f"{tag}_dQ"]) < tol
     assert rel(dc, g[f"{tag}_dP"]) < tol
+
+
+# ---------------------------------------------------------------- dense / time-varying / asymmetric costs
+import cost_cases as CC  # noqa: E402  (tests/cost_cases.py, shared with gen_golden.py case_costs)
+
+
+def oracle_true_obj(mname):
+    return MODELS[mname].true_obj()
+
+
+@pytest.mark.parametrize("name,mode", [(n_, mo) for n_ in CC.SWEEP_SHAPES for mo in CC.SWEEP_MODES[n_]])
+def test_riccati_cost_classes(golden, name, mode):
+    """lqr_backward on the eight cost classes of tests/cost_cases.py (two
+    problems of each in a batch of 16, T = 9) against the reference's sweep as
+    LQRStepFn.forward runs it, c_back formed from x, u inside.  This pins the
+    oracle's reading of an asymmetric C: c_back = C tau + c, not the symmetrised
+    form (lqr_step_explicit.py:635); Q_ux the lower-left block (:80); the
+    asymmetric Q_uu itself into the gain solve (:87-96, pnqp :137; the Cholesky
+    engine reads its lower triangle, lqr_step_backup.py:203).  The reference is
+    finite in every mode on an asymmetric C_uu, so every mode keeps all eight
+    classes (the box keeps C_uu symmetric for m > 1, as the cases define it)."""
+    g = golden("costs_f64")
+    pr = CC.sweep_problem(name, oracle_true_obj, int(g[f"{name}_seed"]))
+    CC.check(g[f"{name}_sum"], pr["C"], pr["c"], pr["C_box"], pr["c_box"], pr["F"], pr["x"], pr["u"])
+    n, m = pr["n"], pr["m"]
+    C, c = (pr["C_box"], pr["c_box"]) if mode == "box" else (pr["C"], pr["c"])
+    kw = {}
+    if mode == "box":
+        kw = dict(u=pr["u"], u_lower=-CC.SWEEP_BOX, u_upper=CC.SWEEP_BOX)
+    elif mode == "chol":
+        kw = dict(m_solver="chol")
+    K, k, _ = lqr.lqr_backward(C, lqr.c_back(C, c, pr["x"], pr["u"]), pr["F"], n, m, **kw)
+    assert rel(K, g[f"{name}_{mode}_K"]) < 1e-9
+    assert rel(k, g[f"{name}_{mode}_k"]) < 1e-9
+
+
+@pytest.mark.parametrize("name", list(CC.MPC_CASES))
+def test_mpc_cost_classes_f64(golden, name):
+    """mpc_forward on the mixed-class MPC fixtures (and rocket at config 3's
+    own 10 iterations) against the reference's fp64 solves."""
+    g = golden("costs_f64")
+    mname, T, Bf, it, bounds, decay, mls, _mixed = CC.MPC_CASES[name]
+    C, c = CC.mpc_costs(name, oracle_true_obj, int(g[f"{name}_seed"]))
+    CC.check(g[f"{name}_sum"], C, c)
+    lo, hi = bounds if bounds else (None, None)
+    x, u, costs, _ = mpc.mpc_forward(MODELS[mname], g[f"{name}_x0"], C, c, T, u_lower=lo, u_upper=hi, lqr_iter=it,
+                                     eps=0.0, not_improved_lim=10 ** 9, linesearch_decay=decay,
+                                     max_linesearch_iter=mls)
+    assert rel(x, g[f"{name}_x"]) < 1e-8
+    assert rel(u, g[f"{name}_u"]) < 1e-8
+    assert rel(costs, g[f"{name}_costs"]) < 1e-8
