@@ -10,5 +10,6 @@ from .definitions import LinDx, QuadCost  # noqa: F401
 from .mpc_explicit import MPC, GradMethods  # noqa: F401
 from .lqr_step_explicit import LQRStep  # noqa: F401
 from . import env_dx, ops  # noqa: F401
+from . import closed_loop  # noqa: F401  (mpc_episode: receding-horizon episodes on device)
 
 __version__ = "0.1.0"

@@ -30,6 +30,7 @@ LANE_SHAPES = ((3, 1), (5, 1), (4, 3), (4, 1), (2, 1), (4, 2), (6, 2), (6, 1))
 MLP_SMALL_SHAPES = tuple(s for s in LANE_SHAPES if s != (6, 2))
 BOUNDS_NONE, BOUNDS_SCALAR, BOUNDS_TENSOR = 0, 1, 2
 SOLVE_INV, SOLVE_CHOL = 0, 1
+WARM_REFERENCE, WARM_SHIFT, WARM_COLD = 0, 1, 2   # DILQR_WARM_*: dilqr_mpc_advance_f32's warm start
 ERRORS = {1: "unsupported shape/model", 2: "invalid argument", 3: "unsupported option combination"}
 
 
@@ -99,6 +100,7 @@ SIGNATURES = {
     "dilqr_mpc_solve_small_f32": ([_i, _i, _i, _vp, _vp, _vp, _vp, _vp, Bounds, _f, _i, _i, _f, _f, _i, MpcState,
                                    _vp], _i),
     "dilqr_mpc_gather_best_f32": ([_i, _i, _i, _i, MpcState, _vp, _vp, _vp], _i),
+    "dilqr_mpc_advance_f32": ([_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "dilqr_get_matrices_f32": ([_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "dilqr_grad_input_f32": ([_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp], _i),

@@ -7,8 +7,9 @@ Everything numeric runs through dilqr.mpc_explicit.MPC (device-resident iLQR
 loop forward, fused implicit backward); the host keeps the reference's control
 flow: warm-start buffers, RMSprop over (learn_q_logit, learn_p, env_params),
 the q/p round robin every 10 epochs.  Out of scope: the
-argparse CLI, CSV logging, pickled checkpoints, the 'nn' LSTM baseline, and the
-'pendulum-complex' NNDynamics variant.
+argparse CLI, CSV logging, pickled checkpoints, the 'nn' LSTM baseline, and
+training on the 'pendulum-complex' NNDynamics variant (IL_Env builds its
+closed-loop data, populate_data2; ILTrainer refuses it).
 """
 import io
 import pickletools
@@ -24,7 +25,9 @@ from .env_dx.cartpole import CartpoleDx
 from .env_dx.pendulum import PendulumDx
 from .mpc_explicit import MPC, GradMethods
 
-_ENVS = {"pendulum": PendulumDx, "cartpole": CartpoleDx}
+_ENVS = {"pendulum": PendulumDx, "cartpole": CartpoleDx,
+         # il_env.py:40-42; data generation only (populate_data, populate_data2): ILTrainer refuses it
+         "pendulum-complex": lambda: PendulumDx(torch.tensor((10., 1., 1., 1.0, 0.1)), simple=False)}
 
 
 # ---------------------------------------------------------------- datasets
@@ -74,7 +77,9 @@ def load_il_dataset(path):
 
 # ---------------------------------------------------------------- IL_Env
 class IL_Env:
-    """il_env.py:31-188 for 'pendulum' and 'cartpole', tensors on `device`."""
+    """il_env.py:31-188 for 'pendulum' and 'cartpole', tensors on `device`;
+    'pendulum-complex' (the 5-parameter pendulum, il_env.py:40-42) for data
+    generation only."""
 
     def __init__(self, env, lqr_iter=100, mpc_T=35, device="cuda"):
         if env not in _ENVS:
@@ -99,7 +104,7 @@ class IL_Env:
         """il_env.py:59-79 (CPU generator, as the reference draws it)."""
         def uniform(shape, low, high):
             return torch.rand(shape) * (high - low) + low
-        if self.env == "pendulum":
+        if self.env in ("pendulum", "pendulum-complex"):
             th = uniform(n_batch, -(1 / 2) * np.pi, (1 / 2) * np.pi)
             thdot = uniform(n_batch, -1., 1.)
             return torch.stack((torch.cos(th), torch.sin(th), thdot), dim=1)
@@ -121,6 +126,40 @@ class IL_Env:
         self.train_data = tau[:n_train]
         self.val_data = tau[n_train:n_train + n_val]
         self.test_data = tau[-n_test:]
+
+    def populate_data2(self, n_train, n_val, n_test, seed=0):
+        """il_env.py:96-151, the closed-loop expert dataset: from each sampled
+        xinit, mpc_T steps of receding-horizon MPC with the true model as
+        planner and plant (solve, apply the first control, warm-start the next
+        solve with the shifted plan, the reference's u_init[-2] = u_init[-3]
+        included), as one batched dilqr.closed_loop.mpc_episode on the GPU;
+        the reference's settings (detach_unconverged=False, eps = dx.mpc_eps,
+        bounds from the model).  Fills train/val/test_data with
+        cat(x[:-1], u) as [n, mpc_T, n_state + n_ctrl] and returns the Episode
+        (the final state and each solve's cost and du norm are in it).
+
+        One deviation: the reference solves each problem alone (batch 1), so
+        its stop rule (max full_du_norm < eps, n_not_improved) is per problem;
+        the batched episode shares it across the batch, as the reference's own
+        batched MPC does.  At a batch of one the two coincide."""
+        from .closed_loop import mpc_episode
+        T, dx, dev = self.mpc_T, self.true_dx, self.device
+        torch.manual_seed(seed)
+        n_total = n_train + n_val + n_test
+        q, p = dx.get_true_obj()
+        xinit = self.sample_xinit(n_batch=n_total).to(dev)
+        Q = torch.diag(q).to(dev).unsqueeze(0).unsqueeze(0).repeat(T, n_total, 1, 1)
+        P = p.to(dev).unsqueeze(0).repeat(T, n_total, 1)
+        solver = MPC(dx.n_state, dx.n_ctrl, T, u_lower=float(dx.lower), u_upper=float(dx.upper),
+                     lqr_iter=self.lqr_iter, verbose=0, exit_unconverged=False, detach_unconverged=False,
+                     linesearch_decay=dx.linesearch_decay, max_linesearch_iter=dx.max_linesearch_iter,
+                     grad_method=self.grad_method, eps=dx.mpc_eps)
+        ep = mpc_episode(solver, xinit, QuadCost(Q, P), dx, steps=T)
+        tau = torch.cat((ep.x[:-1], ep.u), dim=2).transpose(0, 1)
+        self.train_data = tau[:n_train]
+        self.val_data = tau[n_train:n_train + n_val]
+        self.test_data = tau[n_train + n_val:]
+        return ep
 
     def mpc(self, dx, xinit, q, p, u_init=None, eps_override=None, lqr_iter_override=None):
         """il_env.py:153-188."""
@@ -157,6 +196,8 @@ class ILTrainer:
             assert learn_cost or learn_dx
         if mode == "sysid":
             learn_dx = True
+        if env.env not in ("pendulum", "cartpole"):
+            raise NotImplementedError(f"dilqr: IL training on env {env.env!r} is not on the HIP path")
         self.env, self.mode = env, mode
         self.learn_cost, self.learn_dx = learn_cost, learn_dx
         self.n_batch, self.n_train, self.seed = n_batch, n_train, seed

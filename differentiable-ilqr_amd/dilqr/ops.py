@@ -1089,6 +1089,38 @@ def _mpc_solve_polled(sv, model_id, theta, x_init, C, c, u_init, bounds, lqr_ite
                 return
 
 
+# (n, m) of the env_dx models (include/dilqr.h DILQR_MODEL_*)
+MODEL_SHAPES = {N.MODEL_PENDULUM: (3, 1), N.MODEL_CARTPOLE: (5, 1), N.MODEL_ROCKET: (13, 3),
+                N.MODEL_PENDULUM_COMPLEX: (3, 1)}
+WARM_MODES = {"reference": N.WARM_REFERENCE, "shift": N.WARM_SHIFT, "cold": N.WARM_COLD}
+
+
+def mpc_advance(model_id, theta_plant, u_plan, x_cur, u_warm, warm_mode, x_next_log, u_log, C=None, c=None,
+                cost_log=None):
+    """The step between two solves of a closed loop (dilqr_mpc_advance_f32,
+    il_env.py:134-140), one launch, everything in place: x_cur [B,n] becomes the
+    plant's f(x_cur, u_plan[0]) and is copied to x_next_log [B,n]; u_log [B,m]
+    takes u_plan[0] as the solver gave it; u_warm [T,B,m] takes the plan
+    shifted by warm_mode (a key of WARM_MODES or a DILQR_WARM_* value);
+    cost_log [B] (optional, with the solve's C, c) takes the t = 0 stage cost
+    at (x_cur, u_plan[0]).  x_next_log, u_log and cost_log may be rows of
+    larger arrays."""
+    T, B, m = u_plan.shape
+    n = x_cur.shape[-1]
+    # the kernel indexes every operand by the model's own (n, m)
+    if (n, m) != MODEL_SHAPES.get(model_id, (n, m)):
+        raise ValueError(f"dilqr: model {model_id} is (n, m) = {MODEL_SHAPES[model_id]}; got {(n, m)}")
+    want = {"x_cur": (x_cur, (B, n)), "u_warm": (u_warm, (T, B, m)), "x_next_log": (x_next_log, (B, n)),
+            "u_log": (u_log, (B, m)), "cost_log": (cost_log, (B,)), "C": (C, (T, B, n + m, n + m)),
+            "c": (c, (T, B, n + m))}
+    for name, (t, shape) in want.items():
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"dilqr: mpc_advance: {name} must be {shape}, got {tuple(t.shape)}")
+    N.call("dilqr_mpc_advance_f32", int(model_id), T, B, N.ptr(theta_plant), N.ptr(u_plan), N.ptr(x_cur),
+           N.ptr(u_warm), int(WARM_MODES.get(warm_mode, warm_mode)), N.ptr(C), N.ptr(c), N.ptr(x_next_log),
+           N.ptr(u_log), N.ptr(cost_log), N.stream(u_plan.device))
+
+
 def quad_traj_cost(x, u, C, c):
     """util.get_cost for a quadratic cost (util.py:130-153): per problem,
     sum_t 0.5 tau_t^T C_t tau_t + c_t^T tau_t, in torch on the device (the

@@ -409,6 +409,42 @@ int dilqr_mpc_solve_small_f32(int model, int T, int B, const float* theta, const
 int dilqr_mpc_gather_best_f32(int n, int m, int T, int B, dilqr_mpc_state st, float* x_out,
                               float* u_out, void* stream);
 
+/* ---- closed loop: the step between two solves ----------------------------- */
+/* How the next solve's u_init is formed from this solve's plan u [T,B,m]. */
+#define DILQR_WARM_REFERENCE 0   /* il_env.py:139-140: cat(u[1:], 0), then
+                                    u_init[-2] = u_init[-3]: u[T-2] is used twice
+                                    and u[T-1] dropped.  Needs T >= 3 (the
+                                    reference indexes out of range below)        */
+#define DILQR_WARM_SHIFT 1       /* cat(u[1:], 0)                                 */
+#define DILQR_WARM_COLD 2        /* zeros                                         */
+
+/* One step of a receding-horizon episode after a solve (IL_Env.populate_data2,
+   il_env.py:134-140): apply the plan's first control to the plant,
+   x_{s+1} = f(x_s, u_plan[0]; theta_plant) — the model clamps the control
+   inside, as the reference's dx(x, u) does, and x_{s+1} carries the bits of
+   dilqr_rollout_f32's second row —, log the step and shift the plan into the
+   next solve's warm start.  One problem per lane, one launch; x_cur and u_warm
+   are what the next dilqr_mpc_solve_*_f32 / dilqr_mpc_begin_f32 on the stream
+   reads as x_init and u_init.  u_log is the control as the solver gave it
+   (nominal_actions[0]), not the clamped one.
+   Errors, all before any launch: DILQR_E_ARG for a null pointer (C, c and
+   cost_log excepted; cost_log needs both C and c), T < 1, B < 0, an unknown
+   warm_mode, DILQR_WARM_REFERENCE at T < 3, u_warm overlapping u_plan, or a
+   misaligned pointer: u_plan, x_cur, u_warm, C and c 16 bytes, the three log
+   rows (rows of the caller's [steps+1,B,n], [steps,B,m], [steps,B] arrays) 4
+   bytes; DILQR_E_SHAPE for a model without a forward (DILQR_MODEL_LINDX,
+   DILQR_MODEL_MLP, an unknown id).  B = 0 launches nothing. */
+int dilqr_mpc_advance_f32(int model, int T, int B, const float* theta_plant,
+                          const float* u_plan,   /* [T,B,m]  the solve's best controls            */
+                          float* x_cur,          /* [B,n]    in: x_s   out: x_{s+1} (next x_init) */
+                          float* u_warm,         /* [T,B,m]  out: the next solve's u_init         */
+                          int warm_mode,         /* DILQR_WARM_*                                  */
+                          const float* C, const float* c,   /* the solve's cost [T,B,d,d], [T,B,d]; only t = 0 is read; both may be null */
+                          float* x_next_log,     /* [B,n]  row s+1 of the episode's x log         */
+                          float* u_log,          /* [B,m]  row s of the episode's u log           */
+                          float* cost_log,       /* [B]    row s: 0.5 tau^T C_0 tau + c_0^T tau at (x_s, u_s); may be null */
+                          void* stream);
+
 /* ---- learned dynamics: a one-hidden-layer network (ABI 10) ----------------- */
 /* The reference's NNDynamics (dynamics.py:15-130) with len(hidden_sizes) == 1:
      x' = W2 act(W1 [x;u] + b1) + b2   (+ x with passthrough),
