@@ -44,6 +44,19 @@ static __device__ unsigned long long g_stamps[kStampWaves * kStampSlots];
 
 DEV float bound_lo(const Bounds& bd, long long idx) { return bd.mode == DILQR_BOUNDS_TENSOR ? bd.lo_t[idx] : bd.lo; }
 DEV float bound_hi(const Bounds& bd, long long idx) { return bd.mode == DILQR_BOUNDS_TENSOR ? bd.hi_t[idx] : bd.hi; }
+
+// -0.5 (y_i tau_j + tau_i y_j), entry (i, j) of the implicit backward's dC_t
+// (lqr_step_explicit.py:296-303), with both products rounded before they are
+// added: entry (j, i) is then the same bits, as in the reference's
+// -0.5 (a + a^T).  Written as one expression the sum contracts to a fused
+// multiply-add that rounds one product only, a different one in (i, j) and
+// (j, i), and dC_t comes out asymmetric by an ulp.
+DEV float dC_entry(float yi, float tj, float ti, float yj) {
+#pragma clang fp contract(off)
+  const float a = yi * tj;
+  const float b = ti * yj;
+  return -0.5f * (a + b);
+}
 }  // namespace dilqr
 
 #include "dilqr_group.h"   // 16-lanes-per-problem kernels (rocket-sized d <= 16)

@@ -365,7 +365,7 @@ __global__ void __launch_bounds__(64, kGroupWavesPerSimd) k_implicit_backward_gr
       if (valid && r < d) {
         float dCr[d];
 #pragma unroll
-        for (int j = 0; j < d; ++j) dCr[j] = -0.5f * (yr * tau[j] + taur * y[j]);
+        for (int j = 0; j < d; ++j) dCr[j] = dC_entry(yr, tau[j], taur, y[j]);
         st(dC + (tb * d + r) * d, dCr);
         dc[tb * d + r] = -yr;
       }

@@ -259,7 +259,7 @@ __global__ void __launch_bounds__(kBlock) k_implicit_backward(
 #pragma unroll
       for (int i = 0; i < d; ++i) {
 #pragma unroll
-        for (int j = 0; j < d; ++j) dCt[i][j] = -0.5f * (y[i] * tau[j] + tau[i] * y[j]);
+        for (int j = 0; j < d; ++j) dCt[i][j] = dC_entry(y[i], tau[j], tau[i], y[j]);
         dct[i] = -y[i];
       }
       wave_store_records<d * d>(dC + ((size_t)t * B + b0) * d * d,

@@ -1060,14 +1060,275 @@ def case_costs():
         save(f"costs_{tname(dt)}", **out[dt])
 
 
+# --------------------------------------------------------------------------
+# O. the implicit backward on the fifteen cost classes of cost_cases.BACKWARD_CLASSES
+#    (one problem of each, T = 10).  Writes implicit_costs_f64.npz; the costs are
+#    regenerated from the seed (checksum stored)
+# --------------------------------------------------------------------------
+IMPLICIT_COST_CASES = {
+    # tag (its model and the horizon are cost_cases.IMPLICIT_COSTS, IMPLICIT_COSTS_T):
+    # (box half-widths to walk (None: unconstrained), MPC_CASES entry for decay / max_ls)
+    "cart_unc": (None, "cart_unc"),
+    "cart_box": ((5.0, 3.0, 2.0, 1.0), "cart_box10"),
+    "pend_box": ((2.0, 1.5, 1.0, 0.5), "pend_box"),
+    "rock_unc": (None, "rocket_unc"),
+    "rock_box": ((10.0, 7.0, 5.0, 3.0), "rocket_unc"),
+}
+IC_ORACLE_BAR = {"cartpole": 1e-6, "pendulum": 1e-6, "rocket": 2e-5}     # test_implicit_backward_fast_f64's
+IC_F32_BAR = 1e-4 / 3                # the float32 numpy oracle, per problem: a third of the device's bar
+IC_NEAR = (1e-8, 1e-5)               # no control this close to a bound without being on it
+# A last pass that wrongly keeps its registers (or reads C_ux for C_xu) must move
+# the classes aimed at it by ten times the device's bar, measured on the fp64
+# oracle with that pass's C, c replaced (pass_d_variant).  Required of the
+# unconstrained fixtures (in a boxed one a class whose early controls are all
+# active has y = 0 up to the changed step, so nothing to move), recorded for all.
+IC_SENS = 1e-3
+IC_SENS_REQUIRED = {
+    "cartpole": {"c_regs": ("diag_tv", "tinv_dense", "dense", "asym", "asym_t0", "asym_mid", "asym_last",
+                            "diag_mid", "pair_mid"),
+                 "cv_regs": ("diag_cvar", "c_mid"), "xu_T": ("asym", "asym_mid", "asym_last")},
+    "rocket": {"c_regs": ("diag_mid", "pair_mid"), "cv_regs": ("c_mid",), "xu_T": ("asym",)},
+}
+
+
+def pass_d_variant(om, wx, wu, C, c, F, x, u, K_rev, lo, hi, Cd, cd, xu_T=False):
+    """dtheta of oracle.adjoint.implicit_backward_fast with the kernels' last
+    pass reading (Cd, cd) where it should read (C, c): y from the true C, then
+    lam, M_t, w, dlam from (Cd, cd); xu_T: C_ux^T for C_xu in dlam.  dC, dc
+    depend on y alone, so only dtheta can tell."""
+    from oracle import adjoint as oadj
+    from oracle import lqr as olqr
+    T, B, n = wx.shape
+    m = wu.shape[2]
+    d = n + m
+    g = np.concatenate([wx, wu], 2)
+    I = oadj._active_set(u, lo, hi)
+    gD, gd, Dx, Du, *_ = om.grad_input(x, u, K_rev, None)
+    Dtau = np.concatenate([Dx, Du], -1)
+    xu = np.concatenate([x, u], 2)
+
+    def lam_M(C_, c_):
+        lams, prev = [None] * T, None
+        for t in range(T - 1, -1, -1):
+            lam = olqr.bmv(C_[t, :, :n], xu[t]) + c_[t, :, :n]
+            if prev is not None:
+                lam = lam + olqr.bmv(np.swapaxes(F[t, :, :, :n], 1, 2), prev)
+            lams[t] = prev = lam
+        M = np.zeros((T, B, d, d))
+        for t in range(T - 1):
+            M[t] = np.einsum("bi,bijk->bjk", lams[t + 1], Dtau[t])
+        return lams, M
+    y = oadj.adjoint_lqr_linear(C + np.swapaxes(lam_M(C, c)[1], 2, 3), g, F, n, m, I)
+    lams, M = lam_M(Cd, cd)
+    w = g - np.einsum("tbjk,tbj->tbk", M, y)
+    dth, prev = np.zeros((B, om.n_params)), None
+    dlam = [None] * T
+    for t in range(T - 1, -1, -1):
+        Cxu = np.swapaxes(Cd[t, :, n:, :n], 1, 2) if xu_T else Cd[t, :, :n, n:]
+        dl = olqr.bmv(Cd[t, :, :n, :n], y[t, :, :n]) + olqr.bmv(Cxu, y[t, :, n:]) - w[t, :, :n]
+        if prev is not None:
+            dl = dl + olqr.bmv(np.swapaxes(F[t, :, :, :n], 1, 2), prev)
+        dlam[t] = prev = dl
+    for t in range(T - 1):
+        dF = -(dlam[t + 1][:, :, None] * xu[t][:, None, :] + lams[t + 1][:, :, None] * y[t][:, None, :])
+        dth += np.einsum("bnm,bnmk->bk", dF, gD[t]) - np.einsum("bn,bnk->bk", dlam[t + 1], gd[t])
+    return dth
+
+
+def ic_solver(CC, dx, mpc_case, T, C, c, bounds):
+    """solve(x0) for one cost set: the reference's MPC solve rounded to float32
+    and, per problem, the active and free counts, the controls near a bound
+    without being on it, and whether the problem meets the conditions."""
+    _, _, _, _, _, _, _, decay, mls = MPC_CASES[mpc_case]
+    B = C.shape[1]
+    Q, P = torch.tensor(C), torch.tensor(c)
+    kw = {} if bounds is None else dict(u_lower=bounds[0], u_upper=bounds[1])
+    mp = R.mpc_explicit.MPC(dx.n_state, dx.n_ctrl, T, lqr_iter=30, eps=1e-6, linesearch_decay=decay,
+                            max_linesearch_iter=mls, exit_unconverged=False, detach_unconverged=False, verbose=-1,
+                            grad_method=R.mpc_explicit.GradMethods.ANALYTIC, **kw)
+
+    def solve(x0):
+        with torch.no_grad(), contextlib.redirect_stdout(io.StringIO()):
+            x, u, _ = mp(torch.tensor(x0), R.mpc_explicit.QuadCost(Q, P), dx)
+        x, u = CC.f32(np_(x)), CC.f32(np_(u))
+        good = np.isfinite(x).all((0, 2)) & np.isfinite(u).all((0, 2))
+        if bounds is None:
+            return x, u, np.full(B, -1), np.full(B, -1), np.zeros(B, int), good
+        gap = np.minimum(np.abs(u - bounds[0]), np.abs(u - bounds[1]))
+        act = gap <= IC_NEAR[0]
+        na, nf = act.sum((0, 2)), (~act).sum((0, 2))
+        nr = ((gap > IC_NEAR[0]) & (gap < IC_NEAR[1])).sum((0, 2))
+        return x, u, na, nf, nr, good & (na >= 2) & (nf >= 2) & (nr == 0)
+    return solve
+
+
+def ic_walk_x0(CC, mname, B, n, seed, solve):
+    """One box width serves every class only if each problem starts where its
+    own cost saturates some controls and not all: problem b takes the first
+    initial state, walking the x0 seed up from the cost seed, at which it meets
+    the conditions (the problems already placed keep theirs while the rest
+    walk).  Returns x0 [B,n], the seed of each (-1: none in 40)."""
+    x0, x0_seed = np.zeros((B, n)), np.full(B, -1)
+    for s in range(seed, seed + 40):
+        cand = CC.f32(xinit_for(mname, B, np.random.RandomState(s)))
+        good = solve(np.where((x0_seed < 0)[:, None], cand, x0))[5] & (x0_seed < 0)
+        x0[good], x0_seed[good] = cand[good], s
+        if (x0_seed >= 0).all():
+            break
+    return x0, x0_seed
+
+
+def ic_oracles(om, n, m, x, u, wx, wu, C, c, lo, hi, dtype):
+    """implicit_backward_fast in dtype on the fixture; also F and the reversed gains."""
+    from oracle import adjoint as oadj
+    from oracle import lqr as olqr
+    from oracle import mpc as ompc
+    f = lambda a: a.astype(dtype)  # noqa: E731
+    Fo, fo = ompc.linearize(om, f(x), f(u))
+    K, _, _ = olqr.lqr_backward(f(C), olqr.c_back(f(C), f(c), f(x), f(u)), Fo, n, m, u=f(u), u_lower=lo, u_upper=hi)
+    got = oadj.implicit_backward_fast(om, f(wx), f(wu), f(C), f(c), Fo, fo, f(x), f(u), K[::-1], lo, hi)
+    assert all(a.dtype == dtype for a in got)
+    return got, Fo, K[::-1]
+
+
+def ic_sensitivity(CC, om, wx, wu, C, c, Fo, x, u, K_rev, lo, hi, dth):
+    """Per problem, how far dtheta moves when the last pass alone keeps step
+    T-1's diagonal (c_regs), step T-1's c (cv_regs), or reads C_ux^T for C_xu."""
+    T, d = C.shape[0], C.shape[-1]
+    Cr, cr = np.zeros_like(C), np.zeros_like(c)
+    Cr[:], cr[:] = C[T - 1] * np.eye(d), c[T - 1]
+    return {mut: CC.per_problem(pass_d_variant(om, wx, wu, C, c, Fo, x, u, K_rev, lo, hi, Cd, cd, xu_T), dth, 0)
+            for mut, (Cd, cd, xu_T) in {"c_regs": (Cr, c, False), "cv_regs": (C, cr, False),
+                                        "xu_T": (C, c, True)}.items()}
+
+
+def ic_reference(CC, label, mname, T, bounds, cls, x, u, x0, C, c, wx, wu, like):
+    """The reference's backward, one problem at a time.  It cannot run a batch
+    of one (fix_point_equ reads A[1], lqr_step_explicit.py:561), so the batch is
+    the problem twice, the copy with zero loss weights: dtheta is the problem's
+    own.  Then the batch run: the same per-problem dQ, dP, and its dtheta the
+    sum (asserted to 1e-10).  Returns [dQ, dP, dtheta_b] (nan where the
+    reference raised, allowed on an asymmetric class only), raised [B], the
+    batch-vs-singles error of dQ/dP and of the dtheta sum."""
+    dt = torch.float64
+    Q, P = torch.tensor(C), torch.tensor(c)
+    B = len(cls)
+    ref = [np.full_like(a, np.nan) for a in like]
+    raised = np.zeros(B, bool)
+    mask = np.array([1.0, 0.0])[None, :, None]
+    for j in range(B):
+        s = [j, j]
+        try:
+            dQ, dP, dth, _, _ = implicit_once(mname, T, 2, bounds, x[:, s], u[:, s], x0[s], Q[:, s], P[:, s],
+                                              wx[:, s] * mask, wu[:, s] * mask, dt)
+            ref[0][:, j], ref[1][:, j], ref[2][j] = dQ[:, 0], dP[:, 0], dth
+        except Exception as e:        # noqa: BLE001 (recorded by the caller)
+            assert cls[j] in CC.ASYM, (label, cls[j], e)
+            raised[j] = True
+            print(label, f"the reference raised on {cls[j]}: {type(e).__name__}: {e}")
+    ok = np.flatnonzero(~raised)
+    bQ, bP, bth, _, _ = implicit_once(mname, T, ok.size, bounds, x[:, ok], u[:, ok], x0[ok], Q[:, ok], P[:, ok],
+                                      wx[:, ok], wu[:, ok], dt)
+    sum_err = np.max(np.abs(bth - ref[2][ok].sum(0))) / np.max(np.abs(bth))
+    assert sum_err < 1e-10, (label, sum_err)
+    bat_err = max(CC.per_problem(bQ, ref[0][:, ok], 1).max(), CC.per_problem(bP, ref[1][:, ok], 1).max())
+    return ref, raised, bat_err, sum_err
+
+
+def ic_attempt(CC, true_obj, tag, mpc_case, seed, width):
+    """One cost seed and box width of one fixture: the arrays to store (keys
+    without the tag), or None with the failed condition printed."""
+    from oracle import models as omodels
+    mname = CC.IMPLICIT_COSTS[tag]
+    T, cls = CC.IMPLICIT_COSTS_T, list(CC.BACKWARD_CLASSES)
+    B, pp = len(cls), CC.per_problem
+    label = f"  {tag} seed {seed} width {width}:"
+    dx, om = model(mname), omodels.MODELS[mname]
+    n, m = dx.n_state, dx.n_ctrl
+    q, p = true_obj(mname)
+    lo, hi = (-width, width) if width else (None, None)
+    bounds = (lo, hi) if width else None
+    C, c = CC.make_backward_costs(q, p, n, T, cls, seed, sym_uu=width is not None and m > 1)
+    solve = ic_solver(CC, dx, mpc_case, T, C, c, bounds)
+    x0, x0_seed = ic_walk_x0(CC, mname, B, n, seed, solve)
+    if (x0_seed < 0).any():
+        print(label, f"no initial state in 40 for {[cls[j] for j in np.flatnonzero(x0_seed < 0)]} -> next")
+        return None
+    x, u, n_act, n_free, near, good = solve(x0)
+    if not good.all():         # the reference's solve couples the batch (its line search)
+        print(label, f"active {n_act}, free {n_free}, near a bound {near} -> next")
+        return None
+    rng = np.random.RandomState(seed + 1000)
+    wx, wu = CC.f32(rng.normal(size=x.shape)), CC.f32(rng.normal(size=u.shape))
+    # the two oracles and the sensitivity condition, before the (slow) reference
+    o64, Fo, K_rev = ic_oracles(om, n, m, x, u, wx, wu, C, c, lo, hi, np.float64)
+    o32 = ic_oracles(om, n, m, x, u, wx, wu, C, c, lo, hi, np.float32)[0]
+    sens = ic_sensitivity(CC, om, wx, wu, C, c, Fo, x, u, K_rev, lo, hi, o64[2])
+    if bounds is None:
+        weak = [(mut, k, float(sens[mut][cls.index(k)])) for mut, ks in IC_SENS_REQUIRED[mname].items() for k in ks
+                if sens[mut][cls.index(k)] < IC_SENS]
+        if weak:
+            print(label, f"a mutated last pass moves too little: {weak} -> next")
+            return None
+    ref, raised, bat_err, sum_err = ic_reference(CC, label, mname, T, bounds, cls, x, u, x0, C, c, wx, wu, o64)
+    e64 = np.stack([pp(o64[0], ref[0], 1), pp(o64[1], ref[1], 1), pp(o64[2], ref[2], 0)], 1)
+    e64[raised] = np.nan
+    bar = IC_ORACLE_BAR[mname]
+    off = raised | ~(e64.max(1) < bar)
+    # an asymmetric class on which the reference raises or leaves the oracles is kept,
+    # pinned to the fp64 oracle; any other class must meet the bar
+    if any(cls[j] not in CC.ASYM for j in np.flatnonzero(off)):
+        print(label, f"oracle vs reference {e64.max(1)} over {bar:g} on a symmetric class -> next")
+        return None
+    exp = [np.where(off.reshape((1, B) + (1,) * (a.ndim - 2)) if a.ndim > 2 else off[:, None], o, a)
+           for a, o in zip(ref, o64)]
+    e32 = np.stack([pp(o32[0], exp[0], 1), pp(o32[1], exp[1], 1), pp(o32[2], exp[2], 0)], 1)
+    if not e32.max() < IC_F32_BAR:
+        print(label, f"float32 oracle {e32.max(0)} over {IC_F32_BAR:.1e} -> next")
+        return None
+    # the conditions, once more, on what is stored
+    assert bounds is None or (n_act.min() >= 2 and n_free.min() >= 2 and near.max() == 0)
+    assert e32.max() < IC_F32_BAR and np.nanmax(np.where(off[:, None], 0.0, e64)) < bar
+    print(f"  {tag}: seed {seed}, x0 seeds {x0_seed}, width {width}, active {n_act if bounds else '-'}; oracle vs reference "
+          f"dC {np.nanmax(e64[:, 0]):.1e} dc {np.nanmax(e64[:, 1]):.1e} dtheta {np.nanmax(e64[:, 2]):.1e}; "
+          f"float32 oracle dC {e32[:, 0].max():.1e} dc {e32[:, 1].max():.1e} dtheta {e32[:, 2].max():.1e}; "
+          f"batch vs singles dQ/dP {bat_err:.1e}, sum dtheta {sum_err:.1e}; "
+          f"oracle-pinned: {[cls[j] for j in np.flatnonzero(off)]}")
+    for mut, e in sens.items():
+        print(f"    last pass with {mut}: " + " ".join(f"{k} {v:.0e}" for k, v in zip(cls, e) if v > 0))
+    return {"seed": np.array(seed), "width": np.array(width if width else 0.0), "sum": CC.checksum(C, c), "x0": x0,
+            "x0_seed": x0_seed, "x": x, "u": u, "wx": wx, "wu": wu, "dQ": exp[0], "dP": exp[1], "dtheta": exp[2],
+            "pinned": off, "raised": raised, "oracle_err": e64, "f32_err": e32, "n_active": n_act,
+            "sum_err": np.array(sum_err),
+            # the reference's own answer where the expected value is the oracle's
+            "ref_dQ": ref[0][:, off], "ref_dP": ref[1][:, off], "ref_dtheta": ref[2][off],
+            **{f"sens_{mut}": e for mut, e in sens.items()}}
+
+
+def case_implicit_costs():
+    print("O. implicit backward on the cost classes")
+    CC, true_obj = _cost_cases()
+    assert set(IMPLICIT_COST_CASES) == set(CC.IMPLICIT_COSTS)
+    out = {"classes": np.array(CC.BACKWARD_CLASSES)}
+    with default_dtype(torch.float64):
+        for tag, (widths, mpc_case) in IMPLICIT_COST_CASES.items():
+            torch.set_num_threads(1 if CC.IMPLICIT_COSTS[tag] == "rocket" else 8)      # see case_implicit
+            tries = ((seed, width) for seed in range(20) for width in widths or (None,))
+            res = next((r for r in (ic_attempt(CC, true_obj, tag, mpc_case, s, w) for s, w in tries) if r), None)
+            assert res is not None, tag
+            out.update({f"{tag}_{k}": v for k, v in res.items()})
+    save("implicit_costs_f64", **out)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["models", "riccati", "pnqp", "lqrstep", "mpc", "adjoint", "implicit",
-                             "implicit25", "datasets", "il", "generic", "api", "complex", "stepgen", "costs"]
+                             "implicit25", "datasets", "il", "generic", "api", "complex", "stepgen", "costs",
+                             "implicit_costs"]
     table = {"models": case_models, "riccati": case_riccati, "pnqp": case_pnqp,
              "lqrstep": case_lqrstep, "mpc": case_mpc, "mpc_iterates": case_mpc_iterates,
              "adjoint": case_classic_adjoint,
              "implicit": case_implicit, "implicit25": case_implicit25, "datasets": case_datasets, "il": case_il,
              "generic": case_generic, "api": case_api, "complex": case_complex, "stepgen": case_stepgen,
-             "costs": case_costs}
+             "costs": case_costs, "implicit_costs": case_implicit_costs}
     for w in which:
         table[w]()

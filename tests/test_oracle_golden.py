@@ -344,3 +344,121 @@ def test_mpc_cost_classes_f64(golden, name):
     assert rel(x, g[f"{name}_x"]) < 1e-8
     assert rel(u, g[f"{name}_u"]) < 1e-8
     assert rel(costs, g[f"{name}_costs"]) < 1e-8
+
+
+# ---------------------------------------------------------------- the implicit backward on the cost classes
+def implicit_costs_oracle(pr, fn, sel=None):
+    """fn (implicit_backward or implicit_backward_fast) on the problems sel of a fixture."""
+    M = MODELS[pr["mname"]]
+    s = np.arange(len(pr["classes"])) if sel is None else np.asarray(sel)
+    x, u, C, c, wx, wu = (pr[k][:, s] for k in ("x", "u", "C", "c", "wx", "wu"))
+    Fo, fo = mpc.linearize(M, x, u)
+    K, _, _ = lqr.lqr_backward(C, lqr.c_back(C, c, x, u), Fo, pr["n"], pr["m"], u=u, u_lower=pr["lo"], u_upper=pr["hi"])
+    return fn(M, wx, wu, C, c, Fo, fo, x, u, K[::-1], pr["lo"], pr["hi"])
+
+
+def implicit_costs_errors(got, exp):
+    return np.stack([CC.per_problem(got[0], exp[0], 1), CC.per_problem(got[1], exp[1], 1),
+                     CC.per_problem(got[2], exp[2], 0)], 1)
+
+
+@pytest.mark.parametrize("tag", list(CC.IMPLICIT_COSTS))
+def test_implicit_backward_fast_cost_classes(golden, tag):
+    """implicit_backward_fast on the fifteen cost classes (T = 10, one problem of
+    each) against the reference's LQRStep(no_op_forward=True) backward, per
+    problem, at test_implicit_backward_fast_f64's bars.  The reference agrees on
+    every class (asymmetric ones included) to 1e-13, and on rocket
+    unconstrained to 2.5e-6 (dC, dc) and 1.4e-5 (dtheta),
+    except where C_uu itself is asymmetric with m > 1 (rocket unconstrained, the
+    four asym classes): its nested adjoint solve factors Q_uu by Cholesky, which
+    reads one triangle, and its dC, dc, dtheta then leave the LU elimination's
+    by up to 7e-2, 7e-2, 1.4e-1.  Those four problems are pinned to this
+    function's own fp64 value (g["rock_unc_pinned"]); here they are held to the
+    reference's answer being off by what the generator recorded, so that a
+    change of either is seen."""
+    g = golden("implicit_costs_f64")
+    pr = CC.implicit_costs_problem(g, tag, oracle_true_obj)
+    got = implicit_costs_oracle(pr, adjoint.implicit_backward_fast)
+    err = implicit_costs_errors(got, (pr["dQ"], pr["dP"], pr["dtheta"]))
+    pin = pr["pinned"]
+    tol = 2e-5 if pr["mname"] == "rocket" else 1e-6
+    assert err[~pin].max() < tol, dict(zip(pr["classes"], err.max(1)))
+    assert err[pin].max(initial=0.0) < 1e-12
+    assert [pr["classes"][j] for j in np.flatnonzero(pin)] == (list(CC.ASYM) if tag == "rock_unc" else [])
+    if pin.any():
+        sel = np.flatnonzero(pin)
+        off = implicit_costs_errors([got[0][:, sel], got[1][:, sel], got[2][sel]],
+                                    (g[f"{tag}_ref_dQ"], g[f"{tag}_ref_dP"], g[f"{tag}_ref_dtheta"]))
+        assert np.allclose(off, g[f"{tag}_oracle_err"][sel], rtol=1e-6, atol=1e-12)
+        assert off.max() > 1e-3
+
+
+@pytest.mark.parametrize("tag", list(CC.IMPLICIT_COSTS))
+def test_implicit_backward_cost_classes(golden, tag):
+    """The literal restatement (unit right-hand sides, the dense (T d)^2 solve)
+    on the same goldens at test_implicit_backward_f64's bar, per problem.  On
+    rocket it runs a second per problem, so there it runs fewer: of the
+    unconstrained fixture the four asym classes, the problems pinned to the fast
+    algebra, where the literal restatement (the reference's Cholesky engine for
+    m > 1) must meet the reference's own stored answer instead; of the boxed
+    fixture asym and pair_mid against the golden."""
+    g = golden("implicit_costs_f64")
+    pr = CC.implicit_costs_problem(g, tag, oracle_true_obj)
+    if pr["pinned"].any():
+        assert pr["mname"] == "rocket"
+        sel = np.flatnonzero(pr["pinned"])
+        exp = (g[f"{tag}_ref_dQ"], g[f"{tag}_ref_dP"], g[f"{tag}_ref_dtheta"])
+    elif pr["mname"] == "rocket":
+        sel = np.array([pr["classes"].index("asym"), pr["classes"].index("pair_mid")])
+        exp = (pr["dQ"][:, sel], pr["dP"][:, sel], pr["dtheta"][sel])
+    else:
+        sel = np.arange(len(pr["classes"]))
+        assert not pr["pinned"].any()
+        exp = (pr["dQ"], pr["dP"], pr["dtheta"])
+    got = implicit_costs_oracle(pr, adjoint.implicit_backward, sel)
+    err = implicit_costs_errors(got, exp)
+    assert err.max() < 1e-6, dict(zip(np.asarray(pr["classes"])[sel], err.max(1)))
+
+
+@pytest.mark.parametrize("n,m,T", [(3, 1, 10), (5, 1, 10), (13, 3, 10), (5, 1, 2), (13, 3, 3)])
+def test_backward_cost_classes_path_bits(n, m, T):
+    """Each class of BACKWARD_CLASSES is what cost_cases' table says: which of
+    c_offd, c_dif, cv_dif a bitwise scan of the float32 arrays sets (the kernels'
+    first pass, restated in numpy), per problem and, as the rocket kernel
+    decides, per row; where the one changed step is; and the first eight
+    classes are make_costs' own arrays."""
+    mname = {3: "pendulum", 5: "cartpole", 13: "rocket"}[n]
+    q, p = oracle_true_obj(mname)
+    cls = list(CC.BACKWARD_CLASSES)
+    C, c = CC.make_backward_costs(q, p, n, T, cls, 3, sym_uu=m > 1)
+    # (make_costs' draws depend on the batch size, so the comparison keeps it)
+    C8, c8 = CC.make_costs(q, p, n, T, list(CC.CLASSES) + ["tinv_diag"] * (len(cls) - 8), 3, sym_uu=m > 1)
+    assert np.array_equal(C[:, :8], C8[:, :8]) and np.array_equal(c[:, :8], c8[:, :8])
+    assert np.array_equal(C, CC.f32(C)) and np.array_equal(c, CC.f32(c))
+    bits = CC.path_bits(C, c)
+    D = np.diag(CC.f32(q))
+    i = CC.PAIR_STATE[n]
+    for b, k in enumerate(cls):
+        assert tuple(int(v) for v in bits[b].any(0)) == CC.PATH_BITS[k], k
+        if k in CC.CLASSES:
+            continue
+        ts = T // 2 if k.endswith("_mid") else 0
+        rest = [t for t in range(T) if t != ts]
+        assert np.array_equal(C[rest, b], np.broadcast_to(D, (T - 1, n + m, n + m))), k      # diag(q) off the step
+        assert not np.signbit(C[:, b]).any(), k                                        # no -0.0 word
+        if k.startswith("diag_t") or k == "diag_mid":
+            assert np.array_equal(C[ts, b], CC.f32(1.1 * D)) and (c[:, b] == c[0, b]).all()
+        elif k.startswith("c_"):
+            assert np.array_equal(C[ts, b], D) and (c[rest, b] == c[rest[0], b]).all()
+            assert (c[ts, b] != c[rest[0], b]).any()
+        elif k.startswith("pair_"):
+            E = C[ts, b] - D
+            assert E[i, n] == E[n, i] != 0 and np.count_nonzero(E) == 2 and (c[:, b] == c[0, b]).all()
+            # the rocket kernel: only rows i and n leave the register path
+            assert np.flatnonzero(bits[b, :, 0] | bits[b, :, 1]).tolist() == [i, n]
+            # the stage cost stays convex where the state is free
+            assert ts == 0 or np.linalg.eigvalsh(C[ts, b]).min() >= 0
+        else:
+            assert k == "diag_cvar" and np.array_equal(C[ts, b], D) and (np.diff(c[:, b], axis=0) != 0).any(1).all()
+    # pair_t0 is the issue's 0.1
+    assert C[0, cls.index("pair_t0"), i, n] == CC.f32(0.1)
